@@ -30,6 +30,13 @@ Other BASELINE.json configs:
 
 Rank 0 prints ONE JSON line.  Time = max over ranks of the K-step wall time,
 bracketed by a barrier + device synchronize on both sides.
+
+A plain run sets up, warms up, times the K steps and prints that line.
+``--full`` adds the accounting the headline figure does not need (kernel routes
+of the timed steps, DDP bucket layout check, per-bucket all-reduce timing, rank
+spread); ``--dump-outputs DIR`` runs, last of all, two more steps of the timed
+path from the rewound (seeded) state and writes their losses as ``DIR/loss.npy``
+(eager steps only; none of the line's figures includes them).
 """
 from __future__ import annotations
 
@@ -40,6 +47,7 @@ import socket
 import subprocess
 import sys
 import time
+from typing import Optional
 
 import torch
 
@@ -100,6 +108,54 @@ def spawn_ranks(n: int, argv) -> int:
     return rc
 
 
+DUMP_STEPS = 2  # the second loss is the first that the backward pass and the optimizer reach
+
+
+def dump_conflict(cfg: StepConfig, device_type: str) -> Optional[str]:
+    """Why --dump-outputs cannot run with this configuration (None: it can).
+    Captured steps replay cached copies of the weights (ops/wt_cache.py) that a
+    rewind behind the optimizer's back would leave stale."""
+    if device_type == "cuda" and (cfg.graph or cfg.dp_graphs or (cfg.parallel == "pipe" and cfg.pipe_graphs)):
+        return ("--dump-outputs rewinds the weights behind captured graphs' cached copies: run it "
+                "eagerly (no --graph / --dp-graphs; --no-pipe-graphs with --parallel pipe)")
+    return None
+
+
+def rewind(st, start: dict) -> None:
+    """Put the training state back to its seeded start (``start``: a copy of the
+    model's state dict taken before the first step): weights and buffers the way
+    a checkpoint is loaded (utils/checkpoint.py), zero momentum, fp32 masters
+    re-seeded from the weights."""
+    with torch.no_grad():
+        st.model.load_state_dict(start)
+        for group in st.optimizer.state_dict()["flat_state"]:  # the optimizer's own buffers
+            group["momentum"].zero_()
+        st.optimizer.sync_from_params()
+
+
+def dump_outputs(out_dir: Optional[str], st, start: dict) -> None:
+    """--dump-outputs: ``loss.npy``, float32 [DUMP_STEPS]: what the timed path
+    returns for its last DUMP_STEPS steps, which are run here, after the timed
+    ones, from the rewound state.  loss[0] is the forward pass on the seeded
+    weights; loss[1] is the forward pass on the weights that step 0's backward
+    pass, gradient reduction and SGD update (from zero momentum and re-seeded
+    masters) left, so every part of the step reaches the file.
+
+    Why rewound: the reductions use unordered atomics, a rounding-level
+    difference that SGD on random labels amplifies step by step (one build, two
+    runs, 25 steps: loss 0.3 % apart, weights 15 % in relative L2), so what step
+    N returns says nothing about a build.  Steps from the seeded weights on the
+    seeded batch repeat to rounding and do not depend on --steps / --warmup."""
+    import numpy as np
+
+    rewind(st, start)
+    losses = [st.step().detach().float().reshape(()).cpu() for _ in range(DUMP_STEPS)]
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), torch.stack(losses).numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,6 +207,19 @@ def main() -> int:
                     help="activation checkpointing: recompute the block trunk in K segments in "
                          "backward (the reference's '2048(checkpoint)' runs, Readme.md:168,192)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float32): loss.npy, the losses of two more steps of the timed path, run "
+                         "last of all from the seeded start state (weights rewound, momentum zero) "
+                         "on the seeded batch, so that they repeat from run to run and two builds "
+                         "can be compared; the second loss carries the first step's backward pass "
+                         "and optimizer update.  Eager steps only: not with --graph, --dp-graphs "
+                         "or, on a GPU, --parallel pipe without --no-pipe-graphs")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the kernel routes of "
+                         "the timed steps, the DDP bucket layout check across ranks, per-bucket "
+                         "all-reduce timing and the per-rank step spread (config.routes_per_step, "
+                         "ddp_buckets, ddp_comm, rank_step_ms)")
     ap.add_argument("--watchdog", type=float, default=None, metavar="SECONDS",
                     help="exit 1 when the collective stream is stuck this long (default 900 s for "
                          "multi-rank GPU runs without --graph, 0 = off)")
@@ -198,7 +267,12 @@ def main() -> int:
     if args.parallel == "dp" and env.world_size > 1:
         raise SystemExit("--parallel dp is single-process multi-GPU: run `python bench.py --parallel dp "
                          "--gpus N` without torchrun")
+    if args.dump_outputs and dump_conflict(cfg, dev.type):
+        raise SystemExit(dump_conflict(cfg, dev.type))
     st = build_train_state(cfg, dev)
+    # the seeded start state, kept on the host so that it adds nothing to peak_mem_gb
+    start_state = {k: v.detach().to("cpu", copy=True) for k, v in st.model.state_dict().items()} \
+        if args.dump_outputs else None
     comm = default_communicator(dev)
     wd = args.watchdog if args.watchdog is not None else (
         900.0 if env.world_size > 1 and dev.type == "cuda" and not args.graph else 0.0)
@@ -230,11 +304,11 @@ def main() -> int:
             reset_host_times()
     # per-bucket all-reduce timing of every timed backward (DDP only; a captured
     # graph replays without the reducer's host-side launches, so not there)
-    timed_comm = hasattr(st.wrapped, "enable_comm_timing") and not args.graph
+    timed_comm = args.full and hasattr(st.wrapped, "enable_comm_timing") and not args.graph
     if timed_comm:
         st.wrapped.enable_comm_timing(True)
     from distributed_model_parallel_amd.utils import routes
-    routes0 = routes.route_counts()
+    routes0 = routes.route_counts() if args.full else None
     bcast0 = getattr(st.wrapped, "buffer_broadcasts", None)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -255,10 +329,11 @@ def main() -> int:
         st.wrapped.enable_comm_timing(False)
         if "exposed_tail_ms" in ddp_comm:
             ddp_comm["exposed_tail_ms_max_over_ranks"] = round(comm.max_scalar(ddp_comm["exposed_tail_ms"]), 3)
-    rank_step = {"max": round(comm.max_scalar(rank_ms), 3), "min": round(-comm.max_scalar(-rank_ms), 3)}
+    rank_step = {"max": round(comm.max_scalar(rank_ms), 3),
+                 "min": round(-comm.max_scalar(-rank_ms), 3)} if args.full else None
     final_loss = float(loss.item())
     step_routes = {k: round(v / args.steps, 2) for k, v in
-                   sorted(routes.diff(routes.route_counts(), routes0).items())}
+                   sorted(routes.diff(routes.route_counts(), routes0).items())} if args.full else None
     phases = {k: {"ms_per_step": round(v["ms"] / args.steps, 3), "calls_per_step": v["calls"] / args.steps}
               for k, v in phase_summary().items()} if args.phase_times else None
     dp_host = None
@@ -274,7 +349,7 @@ def main() -> int:
     # every rank holds the same (rebuilt) bucket layout -- RCCL would deadlock on a
     # mismatch -- and module buffers cost one broadcast per dtype group per forward
     ddp_facts = None
-    if hasattr(st.wrapped, "bucket_summary"):
+    if args.full and hasattr(st.wrapped, "bucket_summary"):
         ddp_facts = st.wrapped.bucket_summary()
         dig = float(ddp_facts["digest"])
         ddp_facts["same_on_all_ranks"] = comm.max_scalar(dig) == -comm.max_scalar(-dig)
@@ -294,6 +369,11 @@ def main() -> int:
              f"{'DDP' if args.parallel in ('ddp', 'syncbn') else args.parallel.upper()} {args.dtype}"
     ref = REFERENCE_MNV2.get((args.parallel, n, global_batch)) if args.model == "mobilenetv2" else None
     ref = ref or BASELINE_VALUE
+    peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1) if dev.type == "cuda" else None
+    if args.dump_outputs:
+        # last of all: every counter and figure of the result line is taken by now, so the
+        # extra steps reach none of them (every rank takes the steps, rank 0 writes)
+        dump_outputs(args.dump_outputs if env.is_main else None, st, start_state)
     result = {
         "metric": metric,
         "value": round(img_s, 2),
@@ -344,12 +424,12 @@ def main() -> int:
             "miopen_db": args.miopen_db if dev.type == "cuda" else None,
             "first_step_ms": round(first_step_ms, 1) if first_step_ms is not None else None,
             "final_loss": round(final_loss, 4),
-            "routes_per_step": step_routes,
+            "full": args.full,
+            **({"routes_per_step": step_routes} if step_routes is not None else {}),
             **({"ddp_buckets": ddp_facts} if ddp_facts is not None else {}),
             **({"ddp_comm": ddp_comm} if ddp_comm is not None else {}),
-            "rank_step_ms": rank_step,
-            "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)
-            if dev.type == "cuda" else None,
+            **({"rank_step_ms": rank_step} if rank_step is not None else {}),
+            "peak_mem_gb": peak_mem_gb,
         },
     }
     if env.is_main:

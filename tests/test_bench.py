@@ -60,6 +60,69 @@ def test_bench_pipe_reference_four_way_naive():
     assert res["ms_per_step"] > 0
 
 
+def test_bench_dump_outputs_repeat_and_plain_run_is_lean(tmp_path):
+    """--dump-outputs writes loss.npy (float32 [2], under 64 MB): the losses of
+    two steps of the timed path from the rewound, seeded state.  With --warmup 1
+    --steps 1 the run's own two steps started from that state, so the second
+    dumped loss must equal the run's final loss: that holds only if the rewind
+    put back the weights AND the optimizer state (momentum) of the start.  The
+    state being rewound, the file is the same whatever --steps / --warmup were
+    (the CPU path is deterministic).  A plain run carries none of the --full
+    accounting."""
+    import numpy as np
+
+    args = ("--model", "resnet18", "--batch-size", "2", "--image-size", "32")
+    res = [_run(*args, "--dump-outputs", str(tmp_path / "a")),
+           _run(*args, "--dump-outputs", str(tmp_path / "b"), "--steps", "2", "--warmup", "2")]
+    assert [r["steps"] for r in res] == [1, 2]  # a later --steps wins in argparse
+    for r in res:
+        assert r["ms_per_step"] > 0 and r["config"]["full"] is False
+        assert not {"routes_per_step", "ddp_buckets", "ddp_comm", "rank_step_ms"} & set(r["config"])
+    assert os.listdir(tmp_path / "a") == ["loss.npy"] == os.listdir(tmp_path / "b")
+    a, b = (np.load(tmp_path / d / "loss.npy") for d in "ab")
+    assert a.dtype == np.float32 and a.shape == (2,) and np.isfinite(a).all() and a.nbytes <= 64 * 2 ** 20
+    assert np.array_equal(a, b), (a, b)
+    # final_loss is printed to 4 decimals
+    assert abs(float(a[1]) - res[0]["config"]["final_loss"]) <= 1e-4, (a, res[0]["config"]["final_loss"])
+    # the update between the two steps shows: the second loss is not the first ...
+    assert abs(float(a[1]) - float(a[0])) > 1e-3, a
+    # ... and four training steps moved the loss the timed steps saw away from both
+    assert min(abs(res[1]["config"]["final_loss"] - float(x)) for x in b) > 1e-3
+
+
+def test_bench_full_accounting_does_not_count_the_dump_steps(tmp_path):
+    """bench.py --full --dump-outputs: the dump's extra steps come after every
+    counter is read, so the --full figures per timed step are those of the same
+    run without the dump (2 gloo ranks: one buffer broadcast per dtype group per
+    forward, the routes of the timed steps only)."""
+    args = ("--gpus", "2", "--model", "resnet18", "--batch-size", "2", "--image-size", "32", "--full",
+            "--steps", "2")
+    plain, dumped = _run(*args), _run(*args, "--dump-outputs", str(tmp_path / "d"))
+    assert os.listdir(tmp_path / "d") == ["loss.npy"]
+    for r in (plain, dumped):
+        b = r["config"]["ddp_buckets"]
+        assert b["buffer_broadcasts_per_step"] == b["buffer_dtype_groups"] > 0, b
+        assert r["config"]["routes_per_step"], r["config"]
+    assert dumped["config"]["routes_per_step"] == plain["config"]["routes_per_step"]
+    assert dumped["config"]["ddp_buckets"] == plain["config"]["ddp_buckets"]
+    assert dumped["config"]["peak_mem_gb"] == plain["config"]["peak_mem_gb"]
+
+
+def test_bench_dump_outputs_refuses_captured_steps():
+    """Captured steps replay cached weight copies that the rewind would leave
+    stale: --dump-outputs names the conflict for --graph, --dp-graphs and
+    captured pipeline stages on a GPU, and for nothing else."""
+    import bench
+    from distributed_model_parallel_amd.train.step import StepConfig
+
+    for cfg in (StepConfig(graph=True), StepConfig(parallel="dp", dp_graphs=True), StepConfig(parallel="pipe")):
+        assert "--dump-outputs" in bench.dump_conflict(cfg, "cuda"), cfg
+        assert bench.dump_conflict(cfg, "cpu") is None, cfg
+    for cfg in (StepConfig(), StepConfig(parallel="syncbn"), StepConfig(parallel="dp"), StepConfig(parallel="none"),
+                StepConfig(parallel="pipe", pipe_graphs=False)):
+        assert bench.dump_conflict(cfg, "cuda") is None, cfg
+
+
 def test_bench_ddp_label_and_single_rank_comm_flag():
     res = _run("--model", "resnet18", "--batch-size", "2", "--image-size", "32", "--single-rank-comm")
     assert res["config"]["parallelism"] == "ddp1" and res["config"]["single_rank_comm"] is True

@@ -49,11 +49,11 @@ def _check_ddp(d: dict) -> None:
 
 
 def test_resnet50_ddp_8_ranks():
-    _check_ddp(_bench("--model", "resnet50", "--image-size", "32", "--batch-size", "2"))
+    _check_ddp(_bench("--full", "--model", "resnet50", "--image-size", "32", "--batch-size", "2"))
 
 
 def test_resnet50_ddp_syncbn_8_ranks():
-    d = _bench("--model", "resnet50", "--parallel", "syncbn", "--image-size", "32", "--batch-size", "2")
+    d = _bench("--full", "--model", "resnet50", "--parallel", "syncbn", "--image-size", "32", "--batch-size", "2")
     _check_ddp(d)
     assert d["config"]["sync_bn"]
 
