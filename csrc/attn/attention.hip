@@ -29,6 +29,7 @@
 // dQ^T = K^T dS^T over all keys -- no atomics, no dq/dkv kernel split.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

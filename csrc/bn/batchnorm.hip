@@ -32,7 +32,9 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
+#include "../launch.h"
 
 namespace dmp {
 namespace {

@@ -14,13 +14,11 @@
 // where sums over many rows or channels meet (row dots, coefficients).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
+#include "../launch.h"
 
 namespace dmp {
-
-void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
-                               hipStream_t stream);
-
 namespace {
 
 using bf16 = __bf16;

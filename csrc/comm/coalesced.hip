@@ -18,6 +18,7 @@
 #include <mutex>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPCachingAllocator.h>
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

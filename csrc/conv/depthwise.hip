@@ -26,13 +26,11 @@
 //     partials deterministically (no atomics).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
+#include "../launch.h"
 
 namespace dmp {
-
-void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
-                               hipStream_t stream);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -497,9 +495,6 @@ at::Tensor dwconv3x3_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t st
 }
 
 // Weight gradient: returns [C,1,3,3] in `out_dtype`.
-at::Tensor acc_target(const c10::optional<at::Tensor>& out, int64_t numel, at::ScalarType dtype,
-                      const char* who);
-
 at::Tensor dwconv3x3_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t stride,
                            at::ScalarType out_dtype, const c10::optional<at::Tensor>& acc_out) {
   check_nhwc(dy, "dy");

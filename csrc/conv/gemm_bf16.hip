@@ -39,14 +39,11 @@
 #include <cstdlib>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
+#include "../launch.h"
 
 namespace dmp {
-
-// batchnorm.hip: deterministic fp64 reduce of [2][rb][C] partials into [2C+1] moments
-void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
-                               hipStream_t stream);
-
 namespace {
 
 using bf16 = __bf16;
@@ -874,15 +871,6 @@ void launch_tn(const at::Tensor& A, const at::Tensor& B, int M, int N, int K, fl
                        bm, nullptr, nullptr);
   }
 }
-
-}  // namespace
-
-void split_reduce_launch(const float* pp, int splits, int64_t n, at::Tensor& out, hipStream_t stream,
-                         bool acc = false);
-at::Tensor acc_target(const c10::optional<at::Tensor>& out, int64_t numel, at::ScalarType dtype,
-                      const char* who);
-
-namespace {
 
 // C[N, K] = sum_m A[m, :]^T Bmapped[m, :]  -> out [N, K] (bf16 or fp32); with
 // `acc` (a contiguous [N, K] gradient) the split reduce adds into it instead

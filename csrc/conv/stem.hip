@@ -9,6 +9,7 @@
 // TF/s (profiles/conv_roofline_r2.md); the image itself needs no gradient.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

@@ -39,6 +39,7 @@
 // ResNet-50's cuDNN/MIOpen 3x3s (reference model_parallel.py:61).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
 #include <type_traits>
 

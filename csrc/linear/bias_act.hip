@@ -18,6 +18,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "../colreduce.h"
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

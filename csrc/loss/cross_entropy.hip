@@ -11,6 +11,7 @@
 // instead of cast + log_softmax + nll (+ their three backward kernels).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

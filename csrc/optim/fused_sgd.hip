@@ -12,6 +12,7 @@
 // the gradient, dampening applies from the second step on).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
 
 namespace dmp {

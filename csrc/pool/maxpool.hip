@@ -19,7 +19,9 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include "../api.h"
 #include "../common.h"
+#include "../launch.h"
 
 namespace dmp {
 namespace {
@@ -583,10 +585,6 @@ at::Tensor maxpool2d_backward(const at::Tensor& dy, const at::Tensor& idx, int64
                        dy.data_ptr<float>(), idx.data_ptr<uint8_t>(), dx.data_ptr<float>(), g, row_len);
   return dx;
 }
-
-// batchnorm.hip
-void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
-                               hipStream_t stream);
 
 namespace {
 void check_bnpool(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, int64_t k,

@@ -1,4 +1,4 @@
-"""Weight-gradient GEMM on the ping-pong schedule (csrc/gemm/gemm_xl.hip
+"""Weight-gradient GEMM on the ping-pong schedule (csrc/gemm/gemm_tn_xl.hip
 gemm_tn_pp_kernel: m-major LDS planes, transposing LDS reads, split over M)
 against fp32 torch: plain A^T B with ragged M / N / K, and the implicit-GEMM
 conv weight gradient (3x3, strided, 1x1 strided) against autograd."""

@@ -1,5 +1,5 @@
 """the TN weight-gradient gate of ops/linear.py mirrors the
-kernel's operand contract (csrc/gemm/gemm_xl.hip check_bf16_2d), so views the
+kernel's operand contract (csrc/gemm/xl_common.h check_bf16_2d), so views the
 kernel would reject take the library path instead of raising in backward."""
 import torch
 

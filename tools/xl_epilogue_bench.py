@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the fused epilogues of gemm_xl on the ViT-B/16 linears (batch 256,
-50432 tokens): every epilogue mode under the ping-pong (PIPE 7), ring (1) and
-persistent (6) main loops, next to the hipBLASLt + separate-pass sequence it
+50432 tokens): every epilogue mode under the 4-wave (PIPE 11), 8-wave ping-pong
+(10) and ring (1) main loops, next to the hipBLASLt + separate-pass sequence it
 replaces.  HIP events, ms per call."""
 import os
 import sys

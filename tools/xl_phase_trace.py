@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Where a ping-pong GEMM tile's time goes (gemm_xl.hip PIPE 7,
+"""Where a 256 x 256 GEMM tile's time goes (gemm_xl.hip, the 4-wave PIPE 11
+kernel or the 8-wave ping-pong PIPE 10 one, whichever the dispatch picks;
 set_gemm_xl_trace): per block, thread 0 records the realtime clock (10 ns) at
 entry, when the first K tile's operands have landed, after the main loop and
 after the epilogue, plus the HW_ID / XCC_ID registers that name its CU.  This
