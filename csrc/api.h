@@ -243,6 +243,16 @@ std::vector<at::Tensor> layernorm_backward(const at::Tensor& dy, const at::Tenso
                                            const c10::optional<at::Tensor>& dres);
 bool layernorm_supported(int64_t D);
 
+// ---- optim/fused_adamw.hip ----
+void flat_sumsq_partials(const at::Tensor& grad, at::Tensor& partials_row);
+void adamw_prepare(const c10::optional<at::Tensor>& partials, at::Tensor& hyper, at::Tensor& step,
+                   double max_norm, double beta1, double beta2);
+void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                     const at::Tensor& grad, at::Tensor& param,
+                     const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper, double lr,
+                     double beta1, double beta2, double eps, double weight_decay);
+int64_t adamw_grid_cap();  // most blocks adamw_flat_step launches (256 threads, 8 elements each)
+
 // ---- optim/fused_sgd.hip ----
 void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mom,
                    const at::Tensor& grad, const at::Tensor& param, double lr, double wd,

@@ -275,6 +275,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ---- optimizer ----
   m.def("sgd_flat_step", &dmp::sgd_flat_step,
         py::call_guard<py::gil_scoped_release>());
+  m.def("flat_sumsq_partials", &dmp::flat_sumsq_partials, py::arg("grad"), py::arg("partials_row"),
+        "partials_row[b] = block b's sum of squares of the flat gradient (fixed order, no atomics)",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("adamw_prepare", &dmp::adamw_prepare, py::arg("partials"), py::arg("hyper"), py::arg("step"),
+        py::arg("max_norm"), py::arg("beta1"), py::arg("beta2"),
+        "step += 1; hyper = {1 - beta1^step, 1 - beta2^step, gradient norm, clip coefficient}",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("adamw_flat_step", &dmp::adamw_flat_step, py::arg("master"), py::arg("exp_avg"),
+        py::arg("exp_avg_sq"), py::arg("grad"), py::arg("param"), py::arg("decay_mask"), py::arg("hyper"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("adamw_grid_cap", &dmp::adamw_grid_cap);
 
   // ---- coalesced movement ----
   m.def("multi_copy", &dmp::multi_copy,

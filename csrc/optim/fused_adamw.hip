@@ -1,0 +1,290 @@
+// Single-launch AdamW (decoupled weight decay) with global-norm gradient
+// clipping over the same FLAT parameter / gradient buffers fused_sgd.hip works
+// on.  Three kernels per step:
+//   flat_sumsq_partials  one per dtype group: per-block sum of squares of the
+//                        gradient (fp32, fixed order, no atomics)
+//   adamw_prepare        one block: folds all partials in double, advances the
+//                        device-resident step counter, writes the bias
+//                        corrections, the gradient norm and the clip coefficient
+//   adamw_flat_step      one per dtype group: the update itself
+// Step count, bias corrections and clip coefficient never leave the device, so
+// step() has no host sync and a step captured into a hipGraph stays correct on
+// replay (a host scalar would be frozen at capture).  lr is a host scalar, as
+// in the SGD kernel.
+//
+// Every parameter's slot in a flat buffer is padded to 8 elements
+// (ddp/reducer.cpp kAlignElems, MasterAdamW's layout), so an 8-element vector
+// never straddles two parameters: the decay mask has one byte per vector.
+//
+// Semantics: torch.optim.AdamW(amsgrad=False, maximize=False) after
+// torch.nn.utils.clip_grad_norm_.
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+#include "../api.h"
+#include "../common.h"
+
+namespace dmp {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 256 * 8;  // grid cap of adamw_flat_step (as sgd_flat_step)
+
+// hyper[] slots (fp32, device)
+constexpr int kBc1 = 0, kBc2 = 1, kNorm = 2, kClip = 3, kHyper = 4;
+
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, float (&v)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    Vec16<__bf16>::load(reinterpret_cast<const __bf16*>(p), v);
+  } else {
+    float a[4], b[4];
+    Vec16<float>::load(reinterpret_cast<const float*>(p), a);
+    Vec16<float>::load(reinterpret_cast<const float*>(p) + 4, b);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float (&v)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    Vec16<__bf16>::store(reinterpret_cast<__bf16*>(p), v);
+  } else {
+    float a[4] = {v[0], v[1], v[2], v[3]}, b[4] = {v[4], v[5], v[6], v[7]};
+    Vec16<float>::store(reinterpret_cast<float*>(p), a);
+    Vec16<float>::store(reinterpret_cast<float*>(p) + 4, b);
+  }
+}
+
+// Block b sums the squares of its grid-stride share of the vectors and writes
+// out[b]; block 0 also zeroes the slots [gridDim.x, nslots) no block owns.
+template <typename G>
+__global__ __launch_bounds__(kThreads) void flat_sumsq_kernel(const G* __restrict__ grad, int64_t n,
+                                                              float* __restrict__ out, int nslots) {
+  __shared__ float red[kThreads / kWave];
+  const int64_t nvec = n / 8;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+    float g[8];
+    load8(grad + v * 8, g);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = fmaf(g[i], g[i], acc);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < kThreads / kWave; ++i) s += red[i];
+    out[blockIdx.x] = s;
+  }
+  if (blockIdx.x == 0)
+    for (int i = gridDim.x + threadIdx.x; i < nslots; i += blockDim.x) out[i] = 0.f;
+}
+
+template <typename S>
+__global__ __launch_bounds__(kThreads) void adamw_prepare_kernel(const float* __restrict__ partials,
+                                                                 int64_t npart, float* __restrict__ hyper,
+                                                                 S* __restrict__ step, double max_norm,
+                                                                 double beta1, double beta2) {
+  __shared__ double red[kThreads / kWave];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < npart; i += blockDim.x) acc += (double)partials[i];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+#pragma unroll
+  for (int i = 0; i < kThreads / kWave; ++i) total += red[i];
+  const S t = step[0] + 1;
+  step[0] = t;
+  hyper[kBc1] = (float)(1.0 - pow(beta1, (double)t));
+  hyper[kBc2] = (float)(1.0 - pow(beta2, (double)t));
+  if (partials != nullptr) {
+    const double norm = sqrt(total);
+    const double c = max_norm / (norm + 1e-6);
+    hyper[kNorm] = (float)norm;
+    hyper[kClip] = (float)(c > 1.0 ? 1.0 : c);  // a NaN norm stays NaN, as torch's clamp(max=1)
+  } else {
+    hyper[kNorm] = 0.f;
+    hyper[kClip] = 1.f;
+  }
+}
+
+template <typename G, typename P, bool MASTER>
+__global__ __launch_bounds__(kThreads) void adamw_flat_kernel(
+    float* __restrict__ master, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+    const G* __restrict__ grad, P* __restrict__ param, const uint8_t* __restrict__ decay_mask,
+    const float* __restrict__ hyper, int64_t n, float lr, float beta1, float beta2, float omb1,
+    float omb2, float eps, float decay) {
+  // uniform per-step scalars: one load each, then SGPR-resident
+  const float clip = hyper[kClip];
+  const float step_size = lr / hyper[kBc1];
+  const float rsqrt_bc2 = 1.f / sqrtf(hyper[kBc2]);
+  const int64_t nvec = n / 8;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
+    const int64_t o = v * 8;
+    float g[8], w[8], m[8], s[8];
+    load8(grad + o, g);
+    if constexpr (MASTER) load8(master + o, w);
+    else load8(reinterpret_cast<const float*>(param) + o, w);
+    load8(exp_avg + o, m);
+    load8(exp_avg_sq + o, s);
+    const float dk = (decay_mask == nullptr || decay_mask[v] != 0) ? decay : 1.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float gi = g[i] * clip;
+      w[i] *= dk;
+      m[i] = fmaf(beta1, m[i], omb1 * gi);
+      s[i] = fmaf(beta2, s[i], omb2 * gi * gi);
+      // sqrt(v) + eps, not m * rsqrt(v): an exactly-zero gradient history must give 0 / eps = 0
+      const float denom = fmaf(sqrtf(s[i]), rsqrt_bc2, eps);
+      w[i] = fmaf(-step_size, m[i] / denom, w[i]);
+    }
+    store8(exp_avg + o, m);
+    store8(exp_avg_sq + o, s);
+    if constexpr (MASTER) store8(master + o, w);
+    store8(param + o, w);
+  }
+}
+
+void check_flat(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
+}
+
+}  // namespace
+
+int64_t adamw_grid_cap() { return kMaxBlocks; }
+
+// grad: flat gradient (bf16 or fp32), numel a multiple of 8.  partials_row:
+// fp32 [NB]; slot b < blocks holds block b's sum of squares, the rest zero.
+void flat_sumsq_partials(const at::Tensor& grad, at::Tensor& partials_row) {
+  check_flat(grad, "grad");
+  check_flat(partials_row, "partials_row");
+  TORCH_CHECK(partials_row.scalar_type() == at::kFloat && partials_row.numel() >= 1 &&
+                  partials_row.numel() <= INT32_MAX,
+              "partials_row must be a non-empty fp32 tensor");
+  TORCH_CHECK(grad.get_device() == partials_row.get_device(), "grad / partials_row device mismatch");
+  const int64_t n = grad.numel();
+  TORCH_CHECK(n % 8 == 0, "flat buffers must be padded to a multiple of 8 elements");
+  const bool gb = grad.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(gb || grad.scalar_type() == at::kFloat, "grad must be bf16 or fp32");
+  const int nslots = (int)partials_row.numel();
+  const int64_t nvec = n / 8;
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((nvec + kThreads - 1) / kThreads, nslots));
+  auto stream = at::hip::getCurrentHIPStream();
+  float* out = partials_row.data_ptr<float>();
+  if (gb)
+    hipLaunchKernelGGL((flat_sumsq_kernel<__bf16>), dim3(blocks), dim3(kThreads), 0, stream,
+                       reinterpret_cast<const __bf16*>(grad.data_ptr()), n, out, nslots);
+  else
+    hipLaunchKernelGGL((flat_sumsq_kernel<float>), dim3(blocks), dim3(kThreads), 0, stream,
+                       grad.data_ptr<float>(), n, out, nslots);
+}
+
+// partials: fp32 [G, NB] of flat_sumsq_partials rows (undefined: clipping off).
+// hyper: fp32 [4] = {1 - beta1^t, 1 - beta2^t, gradient norm, clip coefficient}.
+// step: int32 / int64 [1], incremented here.
+void adamw_prepare(const c10::optional<at::Tensor>& partials, at::Tensor& hyper, at::Tensor& step,
+                   double max_norm, double beta1, double beta2) {
+  check_flat(hyper, "hyper");
+  check_flat(step, "step");
+  TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() == kHyper, "hyper must be fp32 [4]");
+  TORCH_CHECK(step.numel() == 1 && (step.scalar_type() == at::kInt || step.scalar_type() == at::kLong),
+              "step must be a 1-element int32 / int64 tensor");
+  TORCH_CHECK(step.get_device() == hyper.get_device(), "step / hyper device mismatch");
+  const bool clip = max_norm > 0.0 && partials.has_value() && partials->defined();
+  const float* pp = nullptr;
+  int64_t npart = 0;
+  if (clip) {
+    check_flat(*partials, "partials");
+    TORCH_CHECK(partials->scalar_type() == at::kFloat, "partials must be fp32");
+    TORCH_CHECK(partials->get_device() == hyper.get_device(), "partials / hyper device mismatch");
+    pp = partials->data_ptr<float>();
+    npart = partials->numel();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  if (step.scalar_type() == at::kLong)
+    hipLaunchKernelGGL((adamw_prepare_kernel<int64_t>), dim3(1), dim3(kThreads), 0, stream, pp, npart,
+                       hyper.data_ptr<float>(), step.data_ptr<int64_t>(), max_norm, beta1, beta2);
+  else
+    hipLaunchKernelGGL((adamw_prepare_kernel<int32_t>), dim3(1), dim3(kThreads), 0, stream, pp, npart,
+                       hyper.data_ptr<float>(), step.data_ptr<int32_t>(), max_norm, beta1, beta2);
+}
+
+// master: fp32 flat (or undefined when `param` is fp32 and is its own master)
+// exp_avg / exp_avg_sq: fp32 flat moments; grad / param: bf16 or fp32 flats
+// decay_mask: uint8 [numel / 8], one byte per 8-element vector (undefined:
+// decay everywhere); hyper: as written by adamw_prepare.
+void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                     const at::Tensor& grad, at::Tensor& param,
+                     const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper, double lr,
+                     double beta1, double beta2, double eps, double weight_decay) {
+  const int64_t n = param.numel();
+  check_flat(param, "param");
+  check_flat(grad, "grad");
+  check_flat(exp_avg, "exp_avg");
+  check_flat(exp_avg_sq, "exp_avg_sq");
+  check_flat(hyper, "hyper");
+  TORCH_CHECK(grad.numel() == n && exp_avg.numel() == n && exp_avg_sq.numel() == n,
+              "grad / moment / param size mismatch");
+  TORCH_CHECK(n % 8 == 0, "flat buffers must be padded to a multiple of 8 elements");
+  TORCH_CHECK(exp_avg.scalar_type() == at::kFloat && exp_avg_sq.scalar_type() == at::kFloat,
+              "moments must be fp32");
+  TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() == kHyper, "hyper must be fp32 [4]");
+  const bool gb = grad.scalar_type() == at::kBFloat16, pb = param.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(gb || grad.scalar_type() == at::kFloat, "grad must be bf16 or fp32");
+  TORCH_CHECK(pb || param.scalar_type() == at::kFloat, "param must be bf16 or fp32");
+  const bool has_master = master.has_value() && master->defined();
+  TORCH_CHECK(has_master || !pb, "bf16 parameters need an fp32 master buffer");
+  const int dev = param.get_device();
+  TORCH_CHECK(grad.get_device() == dev && exp_avg.get_device() == dev && exp_avg_sq.get_device() == dev &&
+                  hyper.get_device() == dev, "all buffers must be on one device");
+  float* mp = nullptr;
+  if (has_master) {
+    check_flat(*master, "master");
+    TORCH_CHECK(master->scalar_type() == at::kFloat && master->numel() == n && master->get_device() == dev,
+                "master must be an fp32 flat of the parameters' size");
+    mp = master->data_ptr<float>();
+  }
+  const uint8_t* dm = nullptr;
+  if (decay_mask.has_value() && decay_mask->defined()) {
+    check_flat(*decay_mask, "decay_mask");
+    TORCH_CHECK(decay_mask->scalar_type() == at::kByte && decay_mask->numel() == n / 8 &&
+                    decay_mask->get_device() == dev, "decay_mask must be uint8 [numel / 8]");
+    dm = decay_mask->data_ptr<uint8_t>();
+  }
+  if (n == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  const int64_t nvec = n / 8;
+  const int64_t blocks = std::min<int64_t>((nvec + kThreads - 1) / kThreads, kMaxBlocks);
+  // formed in double, rounded once: what torch's python-float hyper-parameters give
+  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+  const float decay = (float)(1.0 - lr * weight_decay);
+  auto launch = [&](auto gtag, auto ptag) {
+    using G = decltype(gtag);
+    using P = decltype(ptag);
+    const G* gp = reinterpret_cast<const G*>(grad.data_ptr());
+    P* pp = reinterpret_cast<P*>(param.data_ptr());
+    if (has_master)
+      hipLaunchKernelGGL((adamw_flat_kernel<G, P, true>), dim3(blocks), dim3(kThreads), 0, stream, mp,
+                         exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), gp, pp, dm,
+                         hyper.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2, omb1, omb2,
+                         (float)eps, decay);
+    else
+      hipLaunchKernelGGL((adamw_flat_kernel<G, P, false>), dim3(blocks), dim3(kThreads), 0, stream, mp,
+                         exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), gp, pp, dm,
+                         hyper.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2, omb1, omb2,
+                         (float)eps, decay);
+  };
+  if (gb && pb) launch(__bf16{}, __bf16{});
+  else if (gb) launch(__bf16{}, float{});
+  else if (pb) launch(float{}, __bf16{});
+  else launch(float{}, float{});
+}
+
+}  // namespace dmp

@@ -1,19 +1,29 @@
-"""FlatSGD: torch.optim.SGD semantics, one HIP launch per dtype group.
+"""Flat optimizers: torch.optim.SGD / torch.optim.AdamW semantics, one HIP
+launch per dtype group.
 
-Works on the flat parameter / gradient buffers of
+``FlatSGD`` / ``FlatAdamW`` work on the flat parameter / gradient buffers of
 ``DistributedDataParallel(..., flat_parameters=True)``: gradients there are
 already RCCL-averaged bucket views, parameters are views of a flat buffer with
 the same layout, so the update of all 161 ResNet-50 tensors is a single
-vectorised pass (``csrc/optim/fused_sgd.hip``).  bf16 parameter groups keep an
-fp32 master copy and fp32 momentum inside the optimizer; the kernel writes the
-bf16 working weights back in the same pass.
+vectorised pass (``csrc/optim/fused_sgd.hip``, ``csrc/optim/fused_adamw.hip``).
+``MasterSGD`` / ``MasterAdamW`` build the same kind of flat buffers for any
+parameter list.  bf16 parameter groups keep an fp32 master copy and fp32
+optimizer state inside the optimizer; the kernel writes the bf16 working
+weights back in the same pass.
+
+The four classes are a layout (``_DDPLayout`` / ``_ListLayout``: where the
+flats come from, how state follows a bucket rebuild, checkpoint format) times
+an update rule (``_SGDRule`` / ``_AdamWRule``), on the shared ``_FlatOptimizer``
+step.
 
 Reference parity: SGD(lr, momentum 0.9, weight_decay 1e-4) at
-``model_parallel.py:105`` / ``data_parallel.py:90``.
+``model_parallel.py:105`` / ``data_parallel.py:90``.  AdamW
+with decoupled decay off for biases / norm weights and global-norm clipping is
+what every ViT recipe trains with.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -24,19 +34,105 @@ from . import wgrad_stream, wt_cache
 
 class ForeignOptimizerState(ValueError):
     """The state dict was written by another optimizer class (e.g. a
-    torch.optim.SGD state from an older DataParallel run): nothing in it maps
-    onto this optimizer.  ``load_checkpoint`` tolerates only this case; a
-    layout mismatch of our own format stays a hard error."""
+    torch.optim.SGD state from an older DataParallel run, or an AdamW state
+    offered to an SGD class): nothing in it maps onto this optimizer.
+    ``load_checkpoint`` tolerates only this case; a layout mismatch of our own
+    format stays a hard error."""
 
-class FlatSGD(torch.optim.Optimizer):
-    def __init__(self, ddp, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        params = list(ddp._params)
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                        nesterov=nesterov)
-        super().__init__(params, defaults)
+
+# --------------------------------------------------------------------------- #
+# shared step
+# --------------------------------------------------------------------------- #
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What every flat optimizer does around its update rule.
+
+    A *group* is a dict with the flat ``param`` and ``grad`` of one
+    dtype/device group, an fp32 ``master`` when the parameters are not fp32,
+    and one fp32 flat per name in ``STATE_KEYS``.  The layout mixin supplies
+    ``_current_groups`` / ``_slots`` / ``_layout_id``; the rule mixin supplies
+    ``KIND`` / ``STATE_KEYS`` / ``_update``.
+    """
+
+    KIND = ""
+    STATE_KEYS: Tuple[str, ...] = ()
+
+    def _name(self) -> str:
+        return type(self).__name__
+
+    def _alloc_state(self, st: dict) -> None:
+        pflat = st["param"]
+        if pflat.dtype != torch.float32 and self.master_weights:
+            st["master"] = pflat.float()
+        for k in self.STATE_KEYS:
+            st[k] = torch.zeros(pflat.numel(), dtype=torch.float32, device=pflat.device)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        groups = self._current_groups()
+        if groups and groups[0]["param"].is_cuda:
+            wgrad_stream.join(groups[0]["param"].device)  # gradients from the side stream
+        self._update(groups)
+        self._steps += 1
+        # the updated weights' W^T, one launch (ops/wt_cache.py)
+        wt_cache.after_optimizer_step(p for grp in self.param_groups for p in grp["params"])
+        return loss
+
+    @torch.no_grad()
+    def sync_from_params(self) -> None:
+        """Re-seed the fp32 masters from the current working weights.  The masters
+        are snapshotted when the flat state is built, so weights loaded afterwards
+        without optimizer state (the reference's {'net','acc','epoch'} checkpoints,
+        a plain ``model.load_state_dict``) must be adopted here, or the next step
+        would overwrite them with the stale masters."""
+        for st in self._state_groups():
+            if "master" in st:
+                st["master"].copy_(st["param"])
+
+    def _step_count(self) -> int:
+        return self._steps
+
+    def _set_step_count(self, n: int) -> None:
+        self._steps = int(n)
+
+    def _saved_keys(self) -> Tuple[str, ...]:
+        return self.STATE_KEYS + ("master",)
+
+    def _state_header(self) -> dict:
+        sd = {"steps": self._step_count(),
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.KIND != "sgd":  # SGD states keep the format older checkpoints have
+            sd["kind"] = self.KIND
+        return sd
+
+    def _check_kind(self, sd) -> None:
+        kind = sd.get("kind", "sgd") if isinstance(sd, dict) else None
+        if kind != self.KIND:
+            raise ForeignOptimizerState("%s.load_state_dict: the state was written by another kind of "
+                                        "optimizer (%r, this one is %r)" % (self._name(), kind, self.KIND))
+
+    def _load_header(self, sd) -> None:
+        self._set_step_count(sd["steps"])
+        for g, sg in zip(self.param_groups, sd["param_groups"]):
+            g.update(sg)
+
+    @torch.no_grad()
+    def _params_follow_masters(self) -> None:
+        for st in self._state_groups():
+            if "master" in st:  # working weights follow the restored fp32 master
+                st["param"].copy_(st["master"].to(st["param"].dtype))
+
+
+# --------------------------------------------------------------------------- #
+# layouts
+# --------------------------------------------------------------------------- #
+class _DDPLayout:
+    """Flats borrowed from ``DistributedDataParallel(flat_parameters=True)``."""
+
+    def _init_layout(self, ddp, master_weights: bool) -> None:
         self.ddp = ddp
         self.master_weights = master_weights
         self._version = -1
@@ -53,9 +149,7 @@ class FlatSGD(torch.optim.Optimizer):
         new_state = []
         for pflat, gflat in groups:
             st = {"param": pflat, "grad": gflat}
-            if pflat.dtype != torch.float32 and self.master_weights:
-                st["master"] = pflat.float()
-            st["momentum"] = torch.zeros(pflat.numel(), dtype=torch.float32, device=pflat.device)
+            self._alloc_state(st)
             new_state.append(st)
         if old and old_layout is not None:
             self._remap(old, new_state, old_layout, self.ddp.param_layout())
@@ -64,109 +158,70 @@ class FlatSGD(torch.optim.Optimizer):
 
     @torch.no_grad()
     def _remap(self, old, new, old_layout, new_layout) -> None:
-        """Carry momentum / master buffers across a bucket rebuild."""
+        """Carry the state / master buffers across a bucket rebuild."""
         for p, (og, oo), (ng, no) in zip(self.ddp._params, old_layout, new_layout):
             n = p.numel()
-            for key in ("momentum", "master"):
+            for key in self._saved_keys():
                 if key in old[og] and key in new[ng]:
                     new[ng][key].narrow(0, no, n).copy_(old[og][key].narrow(0, oo, n))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _current_groups(self) -> List[dict]:
         self._ensure_state()
-        g = self.param_groups[0]
-        first = self._steps == 0
-        if self._flat_state and self._flat_state[0]["param"].is_cuda:
-            wgrad_stream.join(self._flat_state[0]["param"].device)  # gradients from the side stream
-        for st in self._flat_state:
-            pflat, gflat = st["param"], st["grad"]
-            master = st.get("master")
-            if pflat.is_cuda:
-                _native.require("FlatSGD").sgd_flat_step(
-                    master, st["momentum"], gflat, pflat, float(g["lr"]), float(g["weight_decay"]),
-                    float(g["momentum"]), float(g["dampening"]), bool(g["nesterov"]), 1.0, first)
-            else:
-                _sgd_reference(master, st["momentum"], gflat, pflat, g, first)
-        self._steps += 1
-        # the updated weights' W^T, one launch (ops/wt_cache.py)
-        wt_cache.after_optimizer_step(p for grp in self.param_groups for p in grp["params"])
-        return loss
+        return self._flat_state
+
+    def _state_groups(self) -> List[dict]:
+        return self._flat_state
+
+    def _layout_id(self) -> int:
+        return self._version
+
+    def _slots(self, gi: int):
+        """(parameter, element offset) of every parameter in group `gi`."""
+        return [(p, off) for p, (g, off) in zip(self.ddp._params, self.ddp.param_layout()) if g == gi]
 
     def zero_grad(self, set_to_none: bool = False):
         self.ddp.zero_grad()
 
-    @torch.no_grad()
-    def sync_from_params(self) -> None:
-        """Re-seed the fp32 masters from the current working weights (weights
-        loaded behind the optimizer's back, e.g. a checkpoint without optimizer
-        state); otherwise the next step would write the stale masters back."""
-        for st in self._flat_state:
-            if "master" in st:
-                st["master"].copy_(st["param"])
-
     def state_dict(self):
         self._ensure_state()
-        return {"steps": self._steps, "param_groups": [{k: v for k, v in g.items() if k != "params"}
-                                                       for g in self.param_groups],
-                "flat_state": [{k: v for k, v in st.items() if k in ("momentum", "master")}
-                               for st in self._flat_state],
-                "layout": self.ddp.param_layout()}
+        sd = self._state_header()
+        sd["flat_state"] = [{k: v for k, v in st.items() if k in self._saved_keys()}
+                            for st in self._flat_state]
+        sd["layout"] = self.ddp.param_layout()
+        return sd
 
     def load_state_dict(self, sd):
-        """Restore momentum / master weights parameter by parameter.
+        """Restore state / master weights parameter by parameter.
 
         The saved flats follow the bucket layout of the run that wrote them
         (usually the post-rebuild autograd-ready order), while a fresh DDP
         starts in registration order -- so every parameter's slice is moved
         from ``sd['layout']`` to the current layout, never copied flat-to-flat.
         """
+        self._check_kind(sd)
         if "layout" not in sd or "flat_state" not in sd:
-            raise ForeignOptimizerState("FlatSGD.load_state_dict: not a FlatSGD state (e.g. a "
-                                        "torch.optim.SGD state dict)")
+            raise ForeignOptimizerState("%s.load_state_dict: not a %s state (e.g. a torch.optim "
+                                        "state dict)" % (self._name(), self._name()))
         self._ensure_state()
-        self._steps = sd["steps"]
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            g.update(sg)
-        dev = self._flat_state[0]["momentum"].device if self._flat_state else None
+        self._load_header(sd)
+        dev = self._flat_state[0]["param"].device if self._flat_state else None
         saved = [{k: v.to(dev) for k, v in sst.items()} for sst in sd["flat_state"]]
         old_layout = [tuple(int(v) for v in e) for e in sd["layout"]]
         if len(old_layout) != len(self.ddp._params):
-            raise ValueError("FlatSGD.load_state_dict: checkpoint has %d parameters, model has %d"
-                             % (len(old_layout), len(self.ddp._params)))
+            raise ValueError("%s.load_state_dict: checkpoint has %d parameters, model has %d"
+                             % (self._name(), len(old_layout), len(self.ddp._params)))
         self._remap(saved, self._flat_state, old_layout, self.ddp.param_layout())
-        with torch.no_grad():
-            for st in self._flat_state:
-                if "master" in st:  # working weights follow the restored fp32 master
-                    st["param"].copy_(st["master"].to(st["param"].dtype))
+        self._params_follow_masters()
 
 
-class MasterSGD(torch.optim.Optimizer):
-    """torch.optim.SGD semantics with fp32 master weights for ANY parameter list.
+class _ListLayout:
+    """Flats built here for ANY parameter list: at construction the parameters
+    of each dtype/device group are moved into one flat buffer (parameters
+    become views, channels-last strides preserved) and their ``.grad`` is
+    pre-set to views of a flat gradient buffer, so autograd accumulates in
+    place and the update is one launch per group."""
 
-    Used where there is no DDP flat layout to borrow: single-process
-    DataParallel (its parameters live on ``device_ids[0]``), pipeline stages
-    and plain single-GPU training.  At construction the parameters of each
-    dtype/device group are moved into one flat buffer (parameters become
-    views, channels-last strides preserved) and their ``.grad`` is pre-set to
-    views of a flat gradient buffer, so autograd accumulates in place and the
-    update is ONE ``sgd_flat_step`` launch per group, fp32 master + fp32
-    momentum for bf16 groups (bf16 SGD would drop every update below one
-    bf16 ulp).  Same kernel and numerics as :class:`FlatSGD` under DDP, so DP,
-    pipeline and DDP train at equal precision.
-    """
-
-    def __init__(self, params, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        params = [p for p in params if p.requires_grad]
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                        nesterov=nesterov)
-        super().__init__(params, defaults)
+    def _init_layout(self, params, master_weights: bool) -> None:
         self.master_weights = master_weights
         self._steps = 0
         self._groups = []
@@ -189,10 +244,8 @@ class MasterSGD(torch.optim.Optimizer):
                     gv = gflat.as_strided(p.shape, p.stride(), off)
                     p.grad = gv
                     gviews.append(gv)
-                st = {"params": ps, "offs": offs, "param": pflat, "grad": gflat, "gviews": gviews,
-                      "momentum": torch.zeros(o, dtype=torch.float32, device=dev)}
-                if dt != torch.float32 and master_weights:
-                    st["master"] = pflat.float()
+                st = {"params": ps, "offs": offs, "param": pflat, "grad": gflat, "gviews": gviews}
+                self._alloc_state(st)
                 self._groups.append(st)
 
     @torch.no_grad()
@@ -208,29 +261,20 @@ class MasterSGD(torch.optim.Optimizer):
                 gv.copy_(g)
             p.grad = gv
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        g = self.param_groups[0]
-        first = self._steps == 0
-        if self._groups and self._groups[0]["param"].is_cuda:
-            wgrad_stream.join(self._groups[0]["param"].device)  # gradients from the side stream
+    def _current_groups(self) -> List[dict]:
         for st in self._groups:
             self._adopt_grads(st)
-            pflat, gflat, master = st["param"], st["grad"], st.get("master")
-            if pflat.is_cuda:
-                _native.require("MasterSGD").sgd_flat_step(
-                    master, st["momentum"], gflat, pflat, float(g["lr"]), float(g["weight_decay"]),
-                    float(g["momentum"]), float(g["dampening"]), bool(g["nesterov"]), 1.0, first)
-            else:
-                _sgd_reference(master, st["momentum"], gflat, pflat, g, first)
-        self._steps += 1
-        # the updated weights' W^T, one launch (ops/wt_cache.py)
-        wt_cache.after_optimizer_step(p for grp in self.param_groups for p in grp["params"])
-        return loss
+        return self._groups
+
+    def _state_groups(self) -> List[dict]:
+        return self._groups
+
+    def _layout_id(self) -> int:
+        return 0
+
+    def _slots(self, gi: int):
+        st = self._groups[gi]
+        return list(zip(st["params"], st["offs"]))
 
     def zero_grad(self, set_to_none: bool = False):
         """One fill per group; gradients stay flat views (``set_to_none`` is ignored)."""
@@ -240,42 +284,285 @@ class MasterSGD(torch.optim.Optimizer):
                 if p.grad is not gv:
                     p.grad = gv
 
-    @torch.no_grad()
-    def sync_from_params(self) -> None:
-        """Re-seed the fp32 masters from the current working weights.  The masters
-        are snapshotted at construction, so weights loaded afterwards without
-        optimizer state (the reference's {'net','acc','epoch'} checkpoints, a
-        plain ``model.load_state_dict``) must be adopted here, or the first step
-        would overwrite them with the init weights."""
-        for st in self._groups:
-            if "master" in st:
-                st["master"].copy_(st["param"])
+    def _numels(self):
+        return [[p.numel() for p in st["params"]] for st in self._groups]
 
     def state_dict(self):
-        return {"steps": self._steps,
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
-                "numels": [[p.numel() for p in st["params"]] for st in self._groups],
-                "flat_state": [{k: st[k] for k in ("momentum", "master") if k in st}
-                               for st in self._groups]}
+        sd = self._state_header()
+        sd["numels"] = self._numels()
+        sd["flat_state"] = [{k: st[k] for k in self._saved_keys() if k in st} for st in self._groups]
+        return sd
 
     def load_state_dict(self, sd):
+        self._check_kind(sd)
         if "numels" not in sd or "flat_state" not in sd:
-            raise ForeignOptimizerState("MasterSGD.load_state_dict: not a MasterSGD state (e.g. a "
-                                        "torch.optim.SGD state dict)")
-        if sd["numels"] != [[p.numel() for p in st["params"]] for st in self._groups]:
-            raise ValueError("MasterSGD.load_state_dict: parameter layout differs from the checkpoint")
-        self._steps = sd["steps"]
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            g.update(sg)
+            raise ForeignOptimizerState("%s.load_state_dict: not a %s state (e.g. a torch.optim "
+                                        "state dict)" % (self._name(), self._name()))
+        if sd["numels"] != self._numels():
+            raise ValueError("%s.load_state_dict: parameter layout differs from the checkpoint"
+                             % self._name())
+        self._load_header(sd)
         with torch.no_grad():
             for st, sst in zip(self._groups, sd["flat_state"]):
                 for k, v in sst.items():
                     if k in st:
                         st[k].copy_(v)
-                if "master" in st:
-                    st["param"].copy_(st["master"].to(st["param"].dtype))
+        self._params_follow_masters()
 
 
+# --------------------------------------------------------------------------- #
+# update rules
+# --------------------------------------------------------------------------- #
+class _SGDRule:
+    KIND = "sgd"
+    STATE_KEYS = ("momentum",)
+
+    @staticmethod
+    def _sgd_defaults(lr, momentum, dampening, weight_decay, nesterov) -> dict:
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                    nesterov=nesterov)
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        first = self._steps == 0
+        for st in groups:
+            pflat, gflat, master = st["param"], st["grad"], st.get("master")
+            if pflat.is_cuda:
+                _native.require(self._name()).sgd_flat_step(
+                    master, st["momentum"], gflat, pflat, float(g["lr"]), float(g["weight_decay"]),
+                    float(g["momentum"]), float(g["dampening"]), bool(g["nesterov"]), 1.0, first)
+            else:
+                _sgd_reference(master, st["momentum"], gflat, pflat, g, first)
+
+
+# hyper[] slots written by adamw_prepare (csrc/optim/fused_adamw.hip)
+_BC1, _BC2, _NORM, _CLIP = range(4)
+_SUMSQ_BLOCKS = 1024  # partial sums per group: 4 blocks per CU of an MI355X
+
+
+class _AdamWRule:
+    """torch.optim.AdamW (amsgrad=False, maximize=False), optionally after
+    ``clip_grad_norm_(max_grad_norm)`` over ALL groups of the optimizer.
+
+    The step count, the bias corrections, the gradient norm and the clip
+    coefficient live in device tensors written by ``adamw_prepare``: ``step()``
+    never syncs the host, and a step captured into a hipGraph advances them on
+    every replay.  ``lr`` is passed as a host scalar (a captured graph bakes
+    it, the constant-LR limit of ``--graph``).
+    """
+
+    KIND = "adamw"
+    STATE_KEYS = ("exp_avg", "exp_avg_sq")
+
+    def _adamw_defaults(self, lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d, amsgrad,
+                        maximize) -> dict:
+        if amsgrad or maximize:
+            raise ValueError("%s: amsgrad and maximize are not supported" % self._name())
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("%s: betas must be in [0, 1), got %r" % (self._name(), (b1, b2)))
+        if lr < 0 or eps < 0 or weight_decay < 0:
+            raise ValueError("%s: lr, eps and weight_decay must not be negative" % self._name())
+        self.no_decay_1d = bool(no_decay_1d)
+        self._dev_state: Dict[torch.device, dict] = {}
+        self._partials: Optional[torch.Tensor] = None
+        self._masks: List[Optional[torch.Tensor]] = []
+        self._mask_key = None
+        return dict(lr=lr, betas=(b1, b2), eps=eps, weight_decay=weight_decay,
+                    max_grad_norm=float(max_grad_norm or 0.0))
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("%s supports one param group (decay is switched per parameter by "
+                             "no_decay_1d)" % self._name())
+        super().add_param_group(param_group)
+
+    # ------------------------------------------------------------------ #
+    def _device_state(self, dev: torch.device) -> dict:
+        ds = self._dev_state.get(dev)
+        if ds is None:
+            ds = {"step": torch.full((1,), self._steps, dtype=torch.int64, device=dev),
+                  "hyper": torch.tensor([1.0, 1.0, 0.0, 1.0], dtype=torch.float32, device=dev)}
+            self._dev_state[dev] = ds
+        return ds
+
+    def _clip_devices(self, groups: List[dict]) -> List[torch.device]:
+        devs = list(dict.fromkeys(st["param"].device for st in groups))
+        if self.param_groups[0]["max_grad_norm"] > 0 and len(devs) > 1:
+            raise ValueError("%s: max_grad_norm is a global norm, all parameters must be on one "
+                             "device (got %s)" % (self._name(), ", ".join(str(d) for d in devs)))
+        return devs
+
+    def _decay_masks(self, groups: List[dict]) -> List[Optional[torch.Tensor]]:
+        """One uint8 per 8-element vector of each group's flat: 1 = weight decay
+        applies.  Every parameter's slot is padded to 8 elements, so a vector
+        belongs to one parameter.  ``None``: decay everywhere."""
+        if not self.no_decay_1d:
+            return [None] * len(groups)
+        key = (self._layout_id(), len(groups))
+        if self._mask_key != key:
+            masks = []
+            for gi, st in enumerate(groups):
+                mask = torch.ones(st["param"].numel() // 8, dtype=torch.uint8)
+                for p, off in self._slots(gi):
+                    if off % 8:
+                        raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
+                                           % (self._name(), off))
+                    if p.dim() <= 1:  # biases, LayerNorm / BatchNorm weights
+                        mask[off // 8:(off + p.numel() + 7) // 8] = 0
+                masks.append(mask.to(st["param"].device))
+            self._masks, self._mask_key = masks, key
+        return self._masks
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        clip = float(g["max_grad_norm"] or 0.0)
+        devs = self._clip_devices(groups)
+        if not groups:
+            return
+        masks = self._decay_masks(groups)
+        part = None
+        if clip > 0:
+            part = self._partials
+            if part is None or part.shape[0] != len(groups) or part.device != devs[0]:
+                part = self._partials = torch.zeros(len(groups), _SUMSQ_BLOCKS, dtype=torch.float32,
+                                                    device=devs[0])
+            for i, st in enumerate(groups):
+                if st["grad"].is_cuda:
+                    _native.require(self._name()).flat_sumsq_partials(st["grad"], part[i])
+                else:
+                    _sumsq_reference(st["grad"], part[i])
+        for dev in devs:
+            ds = self._device_state(dev)
+            if dev.type == "cuda":
+                _native.require(self._name()).adamw_prepare(part, ds["hyper"], ds["step"], clip,
+                                                            float(b1), float(b2))
+            else:
+                _adamw_prepare_reference(part, ds["hyper"], ds["step"], clip, b1, b2)
+        for st, mask in zip(groups, masks):
+            pflat = st["param"]
+            hyper = self._dev_state[pflat.device]["hyper"]
+            if pflat.is_cuda:
+                _native.require(self._name()).adamw_flat_step(
+                    st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, mask, hyper,
+                    float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]))
+            else:
+                _adamw_reference(st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat,
+                                 mask, hyper, g)
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Total gradient norm of the last step as a device scalar (reading it is
+        the caller's sync); ``None`` while clipping is off or before a step."""
+        if not self.param_groups[0]["max_grad_norm"] > 0 or not self._dev_state:
+            return None
+        return next(iter(self._dev_state.values()))["hyper"][_NORM]
+
+    # the step count is the device tensor's: a replayed graph advances only that
+    def _step_count(self) -> int:
+        if self._dev_state:
+            return int(next(iter(self._dev_state.values()))["step"].item())
+        return self._steps
+
+    def _set_step_count(self, n: int) -> None:
+        self._steps = int(n)
+        for ds in self._dev_state.values():
+            ds["step"].fill_(int(n))
+
+
+# --------------------------------------------------------------------------- #
+# the four optimizers
+# --------------------------------------------------------------------------- #
+class FlatSGD(_SGDRule, _DDPLayout, _FlatOptimizer):
+    def __init__(self, ddp, lr: float, momentum: float = 0.0, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
+        defaults = self._sgd_defaults(lr, momentum, dampening, weight_decay, nesterov)
+        super().__init__(list(ddp._params), defaults)
+        self._init_layout(ddp, master_weights)
+
+
+class MasterSGD(_SGDRule, _ListLayout, _FlatOptimizer):
+    """torch.optim.SGD semantics with fp32 master weights for ANY parameter list.
+
+    Used where there is no DDP flat layout to borrow: single-process
+    DataParallel (its parameters live on ``device_ids[0]``), pipeline stages
+    and plain single-GPU training.  The update is ONE ``sgd_flat_step`` launch
+    per dtype/device group, fp32 master + fp32 momentum for bf16 groups (bf16
+    SGD would drop every update below one bf16 ulp).  Same kernel and numerics
+    as :class:`FlatSGD` under DDP, so DP, pipeline and DDP train at equal
+    precision.
+    """
+
+    def __init__(self, params, lr: float, momentum: float = 0.0, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
+        defaults = self._sgd_defaults(lr, momentum, dampening, weight_decay, nesterov)
+        params = [p for p in params if p.requires_grad]
+        super().__init__(params, defaults)
+        self._init_layout(params, master_weights)
+
+
+class FlatAdamW(_AdamWRule, _DDPLayout, _FlatOptimizer):
+    """AdamW + global-norm clipping on the DDP flat buffers (twin of :class:`FlatSGD`).
+
+    ``no_decay_1d`` switches weight decay off for parameters with ``ndim <= 1``
+    (biases, LayerNorm / BatchNorm weights) and nothing else: a ViT's
+    ``cls_token`` and ``pos_embedding`` are 3-D and keep decay, as in
+    torchvision's reference recipe.  ``max_grad_norm`` (``None`` / 0 = off)
+    clips the gradient of the whole model to that norm before the update.
+    """
+
+    def __init__(self, ddp, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 max_grad_norm: Optional[float] = None, no_decay_1d: bool = True,
+                 master_weights: bool = True, amsgrad: bool = False, maximize: bool = False):
+        defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
+                                        amsgrad, maximize)
+        super().__init__(list(ddp._params), defaults)
+        self._init_layout(ddp, master_weights)
+
+
+class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
+    """:class:`FlatAdamW` for ANY parameter list (twin of :class:`MasterSGD`)."""
+
+    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None,
+                 no_decay_1d: bool = True, master_weights: bool = True, amsgrad: bool = False,
+                 maximize: bool = False):
+        defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
+                                        amsgrad, maximize)
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            if len(params) > 1:
+                raise ValueError("MasterAdamW supports one param group (decay is switched per "
+                                 "parameter by no_decay_1d)")
+            params = list(params[0]["params"])
+        params = [p for p in params if p.requires_grad]
+        super().__init__(params, defaults)
+        self._init_layout(params, master_weights)
+        self._clip_devices(self._groups)
+
+
+def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 0.9,
+                    weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                    clip_grad_norm: float = 0.0):
+    """The trainer's optimizer: ``kind`` sgd | adamw; ``flat`` picks the DDP-flat
+    class (``target`` is the DDP wrapper) over the parameter-list one."""
+    if kind == "sgd":
+        if clip_grad_norm:
+            raise ValueError("gradient clipping needs optimizer='adamw'")
+        return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    if kind == "adamw":
+        return (FlatAdamW if flat else MasterAdamW)(target, lr=lr, betas=betas, eps=eps,
+                                                    weight_decay=weight_decay,
+                                                    max_grad_norm=clip_grad_norm or None)
+    raise ValueError(f"unknown optimizer {kind!r} (sgd | adamw)")
+
+
+# --------------------------------------------------------------------------- #
+# PyTorch implementations of the kernels (CPU path / test oracle)
+# --------------------------------------------------------------------------- #
 def _sgd_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: torch.Tensor,
                    param: torch.Tensor, g: dict, first: bool) -> None:
     """PyTorch implementation of the flat kernel (CPU path / test oracle)."""
@@ -288,5 +575,50 @@ def _sgd_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: torc
             mom.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
         d = d + g["momentum"] * mom if g["nesterov"] else mom
     w.add_(d.to(w.dtype), alpha=-g["lr"])
+    if master is not None:
+        param.copy_(master.to(param.dtype))
+
+
+def _sumsq_reference(grad: torch.Tensor, partials_row: torch.Tensor) -> None:
+    partials_row.zero_()
+    partials_row[0] = grad.float().pow(2).sum()
+
+
+def _adamw_prepare_reference(partials: Optional[torch.Tensor], hyper: torch.Tensor, step: torch.Tensor,
+                             max_norm: float, beta1: float, beta2: float) -> None:
+    step += 1
+    t = int(step.item())
+    hyper[_BC1] = 1.0 - float(beta1) ** t
+    hyper[_BC2] = 1.0 - float(beta2) ** t
+    if max_norm > 0 and partials is not None:
+        norm = partials.double().sum().sqrt()
+        hyper[_NORM] = norm.float()
+        hyper[_CLIP] = (max_norm / (norm + 1e-6)).clamp(max=1.0).float()
+    else:
+        hyper[_NORM] = 0.0
+        hyper[_CLIP] = 1.0
+
+
+def _adamw_reference(master: Optional[torch.Tensor], exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                     grad: torch.Tensor, param: torch.Tensor, decay_mask: Optional[torch.Tensor],
+                     hyper: torch.Tensor, g: dict) -> None:
+    """PyTorch implementation of adamw_flat_step, fp32 like the kernel."""
+    w = master if master is not None else param
+    b1, b2 = g["betas"]
+    wf = w if w.dtype == torch.float32 else w.float()
+    gr = grad.float() * hyper[_CLIP]
+    decay = 1.0 - g["lr"] * g["weight_decay"]
+    if decay_mask is None:
+        wf.mul_(decay)
+    else:
+        keep = decay_mask.repeat_interleave(8) != 0
+        wf.mul_(torch.where(keep, torch.tensor(decay, dtype=torch.float32, device=wf.device),
+                            torch.ones((), dtype=torch.float32, device=wf.device)))
+    exp_avg.mul_(b1).add_(gr, alpha=1 - b1)
+    exp_avg_sq.mul_(b2).addcmul_(gr, gr, value=1 - b2)
+    denom = (exp_avg_sq.sqrt() / hyper[_BC2].sqrt()).add_(g["eps"])  # sqrt(v) + eps: 0 / eps = 0
+    wf.sub_((g["lr"] / hyper[_BC1]) * (exp_avg / denom))
+    if wf is not w:
+        w.copy_(wf.to(w.dtype))
     if master is not None:
         param.copy_(master.to(param.dtype))

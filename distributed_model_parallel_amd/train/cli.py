@@ -31,6 +31,33 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 
+def _betas(text: str):
+    try:
+        b1, b2 = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected B1,B2 (two numbers), got {text!r}")
+    return b1, b2
+
+
+def check_args(parser: argparse.ArgumentParser, args) -> None:
+    """Flag combinations that cannot run (parser errors, before any process starts)."""
+    if args.clip_grad_norm < 0:
+        parser.error("--clip-grad-norm must not be negative")
+    if args.clip_grad_norm and args.optimizer != "adamw":
+        parser.error("--clip-grad-norm needs --optimizer adamw")
+    world = args.world_size or int(os.environ.get("WORLD_SIZE", "1"))
+    if args.clip_grad_norm and args.parallel == "pipe" and world > 1:
+        parser.error("--clip-grad-norm with --parallel pipe at world size > 1 is not supported "
+                     "(a pipeline's global norm needs a cross-stage reduction)")
+
+
+def _optimizer(args, target, flat: bool):
+    from ..ops.optim import build_optimizer
+    return build_optimizer(args.optimizer, target, flat, lr=args.lr, momentum=args.momentum,
+                           weight_decay=args.weight_decay, betas=args.betas, eps=args.eps,
+                           clip_grad_norm=args.clip_grad_norm)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native data / model parallel training")
     p.add_argument("data", nargs="?", default="", metavar="DIR", help="dataset root (empty: synthetic)")
@@ -46,6 +73,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-j", "--workers", default=4, type=int)
     p.add_argument("--wd", "--weight-decay", default=1e-4, type=float, dest="weight_decay")
     p.add_argument("--momentum", default=0.9, type=float)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
+                   help="adamw: decoupled weight decay (off for biases / norm weights), e.g. --lr 1e-3 --wd 0.05")
+    p.add_argument("--betas", default=(0.9, 0.999), type=_betas, metavar="B1,B2", help="--optimizer adamw")
+    p.add_argument("--eps", default=1e-8, type=float, help="--optimizer adamw")
+    p.add_argument("--clip-grad-norm", default=0.0, type=float, metavar="X",
+                   help="--optimizer adamw: clip the global gradient norm to X (0 = off)")
     p.add_argument("-r", "--resume", action="store_true")
     p.add_argument("--arch", default="mobilenetv2")
     p.add_argument("--parallel", default="ddp", choices=["ddp", "dp", "pipe", "none"])
@@ -86,8 +119,7 @@ def _datasets(args):
     from ..data import DatasetCollection, transforms as T
     cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
     if args.synthetic or not args.data:
-        kind = "SyntheticCIFAR" if cifar or args.arch.startswith("mobilenet") else "Synthetic"
-        return DatasetCollection(kind, "").init()
+        return DatasetCollection(_synthetic_kind(args), "").init()
     if cifar:
         tr, va = T.cifar_train_transform(), T.cifar_test_transform()
     else:
@@ -95,11 +127,23 @@ def _datasets(args):
     return DatasetCollection(args.dataset_type, args.data, tr, va).init()
 
 
+def _synthetic_kind(args) -> str:
+    """Synthetic data of the dataset type's shape -- except for a ViT, whose position
+    embedding fixes the input size: it gets data of the model's own shape and class count."""
+    if args.arch.startswith("vit"):
+        from ..models import INPUT_SHAPES
+        return "SyntheticCIFAR" if INPUT_SHAPES[args.arch][0][1] == 32 else "Synthetic"
+    cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
+    return "SyntheticCIFAR" if cifar or args.arch.startswith("mobilenet") else "Synthetic"
+
+
 def _lr_steps(args):
     return [int(v) for v in args.lr_steps.split(",") if v.strip()] if args.lr_steps else None
 
 
 def _num_classes(args) -> int:
+    if (args.synthetic or not args.data) and args.arch.startswith("vit"):
+        return 10 if _synthetic_kind(args) == "SyntheticCIFAR" else 1000
     return {"CIFAR10": 10, "SyntheticCIFAR": 10, "CUB200": 200, "Place365": 365}.get(
         args.dataset_type, 10 if (args.synthetic or not args.data) and args.arch.startswith("mobilenet") else 1000)
 
@@ -108,7 +152,6 @@ def _num_classes(args) -> int:
 def run_data_parallel(args, env) -> None:
     from ..data import prepare_dataloaders
     from ..models import build_model
-    from ..ops.optim import FlatSGD, MasterSGD
     from ..parallel.data_parallel import DataParallel
     from ..parallel.distributed import DistributedDataParallel
     from ..parallel.sync_batchnorm import SyncBatchNorm
@@ -136,11 +179,10 @@ def run_data_parallel(args, env) -> None:
         cast_model(model, dtype)
     if args.parallel == "ddp":
         net = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb, flat_parameters=True)
-        opt = FlatSGD(net, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+        opt = _optimizer(args, net, flat=True)
     else:
-        # fp32 master weights for bf16 models: same update as DDP's FlatSGD
-        opt = MasterSGD(model.parameters(), lr=args.lr, momentum=args.momentum,
-                        weight_decay=args.weight_decay)
+        # fp32 master weights for bf16 models: same update as DDP's flat optimizer
+        opt = _optimizer(args, model.parameters(), flat=False)
         net = DataParallel(model, graphs=args.dp_graphs) if args.parallel == "dp" else model
     sched = build_schedule(opt, args.epochs, args.warmup_epochs, _lr_steps(args), args.lr_gamma)
     from ..utils.debug import rank0_first
@@ -194,10 +236,13 @@ def run_data_parallel(args, env) -> None:
         if env.is_main and va > best:
             best = va
             save_checkpoint(args.checkpoint, net, opt, sched, epoch, best)
+        extra = {}
+        if args.clip_grad_norm and opt.last_grad_norm is not None:
+            extra["grad_norm"] = float(opt.last_grad_norm)  # the epoch's last step; one read per epoch
         logger.log(epoch, loss_train=lm.avg, acc1_train=am.avg, loss_val=vl, acc1_val=va,
                    time_per_batch=step_s + data_s, time_load_perbatch=data_s,
                    images_per_sec=(args.batch_size * max(1, env.world_size if args.parallel == "ddp" else 1))
-                   / max(step_s + data_s, 1e-9), lr=opt.param_groups[0]["lr"])
+                   / max(step_s + data_s, 1e-9), lr=opt.param_groups[0]["lr"], **extra)
 
 
 @torch.no_grad()
@@ -244,7 +289,6 @@ def run_pipeline(args, env) -> None:
     from ..comm.rccl import Communicator
     from ..data import prepare_dataloaders
     from ..models import INPUT_SHAPES, build_model
-    from ..ops.optim import MasterSGD
     from ..parallel.pipeline import Pipeline
     from ..utils.checkpoint import save_checkpoint, stage_checkpoint_path
     from ..utils.logging import MetricsLogger
@@ -262,8 +306,7 @@ def run_pipeline(args, env) -> None:
                     channels_last=args.channels_last, partition=args.partition,
                     # one GPU only (see train/step.py): multi-rank GPU pipelines run eagerly
                     graphs=env.device.type == "cuda" and not args.no_pipe_graphs and comm.size == 1)
-    opt = MasterSGD(pipe.module.parameters(), lr=args.lr, momentum=args.momentum,
-                    weight_decay=args.weight_decay)
+    opt = _optimizer(args, pipe.module.parameters(), flat=False)
     sched = build_schedule(opt, args.epochs, args.warmup_epochs, _lr_steps(args), args.lr_gamma)
     logger = MetricsLogger(args.log_dir, f"pipe_{args.arch}", env.rank, text_file=f"{args.batch_size}.txt")
     if env.rank == 0:
@@ -327,9 +370,13 @@ def run_pipeline(args, env) -> None:
         save_checkpoint(stage_checkpoint_path(args.checkpoint, env.rank), pipe.module, opt, sched, epoch,
                         all_ranks=True)
         if env.rank == 0:
+            extra = {}
+            if args.clip_grad_norm and opt.last_grad_norm is not None:
+                extra["grad_norm"] = float(opt.last_grad_norm)
             logger.log(epoch, loss_train=loss_s / max(n_train, 1), acc1_train=acc_s / max(n_train, 1),
                        loss_val=vl / max(n_val, 1), acc1_val=va / max(n_val, 1),
-                       time_per_batch=tot_t / max(n_train, 1), time_load_perbatch=tot_d / max(n_train, 1))
+                       time_per_batch=tot_t / max(n_train, 1), time_load_perbatch=tot_d / max(n_train, 1),
+                       **extra)
 
 
 def _spawn_entry(rank: int, world: int, args) -> None:
@@ -378,7 +425,9 @@ def start_watchdog(seconds: Optional[float], env):
 
 
 def main(argv: Optional[list] = None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_args(parser, args)
     if args.parallel == "pipe" and args.world_size and "RANK" not in os.environ:
         import torch.multiprocessing as mp
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from ..models import INPUT_SHAPES, build_model
 from ..ops.loss import cross_entropy
-from ..ops.optim import FlatSGD, MasterSGD
+from ..ops.optim import build_optimizer
 from ..utils.precision import cast_model
 
 
@@ -40,6 +40,10 @@ class StepConfig:
     lr: float = 0.1
     momentum: float = 0.9
     weight_decay: float = 1e-4
+    optimizer: str = "sgd"          # sgd | adamw (ops/optim.py)
+    betas: tuple = (0.9, 0.999)     # optimizer == "adamw"
+    eps: float = 1e-8               # optimizer == "adamw"
+    clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -74,6 +78,12 @@ def synthetic_batch(cfg: StepConfig, device: torch.device, generator_seed: int =
         x = x.contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, ncls, (b,), generator=g).to(device)
     return x, y
+
+
+def _optimizer(cfg: StepConfig, target, flat: bool) -> torch.optim.Optimizer:
+    return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
+                           weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
+                           clip_grad_norm=cfg.clip_grad_norm)
 
 
 def build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
@@ -128,7 +138,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
         wrapped = DistributedDataParallel(model, bucket_cap_mb=cfg.bucket_cap_mb,
                                           first_bucket_mb=cfg.first_bucket_mb,
                                           flat_parameters=True)
-        opt = FlatSGD(wrapped, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
+        opt = _optimizer(cfg, wrapped, flat=True)
 
         def step() -> torch.Tensor:
             out = wrapped(x)
@@ -139,9 +149,8 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
             return loss
     elif cfg.parallel == "dp":
         from ..parallel.data_parallel import DataParallel
-        # fp32 master weights + momentum, one launch per dtype group (same update as DDP's FlatSGD)
-        opt = MasterSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                        weight_decay=cfg.weight_decay)
+        # fp32 master weights + state, one launch per dtype group (same update as DDP's flat optimizer)
+        opt = _optimizer(cfg, model.parameters(), flat=False)
         reps = max(1, cfg.dp_replicas)
         wrapped = DataParallel(model, device_ids=[d for d in range(ndp) for _ in range(reps)]
                                if device.type == "cuda" else None, graphs=cfg.dp_graphs)
@@ -155,8 +164,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
             return loss
     else:
         wrapped = model
-        opt = MasterSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                        weight_decay=cfg.weight_decay)
+        opt = _optimizer(cfg, model.parameters(), flat=False)
 
         def step() -> torch.Tensor:
             out = model(x)
@@ -176,7 +184,7 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
     model-parallel run feeds 512 images per step through 4 stages,
     ``model_parallel.py:92``); it is cut into ``cfg.micro_batches`` micro-batches
     scheduled naive / gpipe / 1f1b.  Every stage updates its own slice with the
-    same fp32-master SGD as the data-parallel paths.  ``step()`` returns the
+    same fp32-master optimizer as the data-parallel paths.  ``step()`` returns the
     loss on rank 0 (and a zero tensor elsewhere).
     """
     from ..comm.rccl import default_communicator
@@ -200,8 +208,10 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
                     # but never with RCCL between captured stages (a 1-GPU box cannot
                     # host two RCCL ranks), so multi-rank GPU pipelines run eagerly
                     graphs=cfg.pipe_graphs and device.type == "cuda" and comm.size == 1)
-    opt = MasterSGD(pipe.module.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                    weight_decay=cfg.weight_decay)
+    if cfg.clip_grad_norm and comm.size > 1:
+        raise ValueError("clip_grad_norm with a multi-stage pipeline needs a cross-stage norm reduction "
+                         "(not implemented)")
+    opt = _optimizer(cfg, pipe.module.parameters(), flat=False)
     x, y = synthetic_batch(cfg, device) if pipe.is_first else (None, None)
     zero = torch.zeros((), device=device)
 

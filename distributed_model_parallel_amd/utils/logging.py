@@ -19,10 +19,11 @@ from typing import Any, Dict, Optional
 
 def reference_line(epoch: int, rec: Dict[str, Any]) -> str:
     """``step:E  loss_train:..  acc1_train:..  loss_val:..  acc1_val:..[  time_per_batch:..
-    time_load_perbatch:..]`` exactly in the reference's key order."""
+    time_load_perbatch:..]`` exactly in the reference's key order; ``grad_norm`` follows
+    when the run clips gradients (the reference has no such field)."""
     parts = [f"step:{epoch}"]
     for k in ("loss_train", "acc1_train", "loss_val", "acc1_val", "time_per_batch",
-              "time_load_perbatch"):
+              "time_load_perbatch", "grad_norm"):
         if k in rec and rec[k] is not None:
             parts.append(f"{k}:{rec[k]}")
     return "  ".join(parts)

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Achieved HBM bandwidth of the flat optimizer kernels, HIP-event timed:
+
+* ``sgd_flat_step``  momentum, bf16 gradient + bf16 weights + fp32 master:
+  reads g(2) w(4) m(4), writes m(4) w(4) p(2) = 20 B per element -- the
+  yardstick, in the same process;
+* ``adamw_flat_step`` bf16 + master, per-vector decay mask: reads g(2) w(4)
+  m(4) v(4), writes m(4) v(4) w(4) p(2) = 28 B per element (+ 0.125 B mask);
+* ``flat_sumsq_partials`` bf16 gradient: 2 B per element;
+
+on flats of ResNet-50 size (25.6 M elements) and ViT-B/16 size (86.6 M).  Both
+update kernels stream 0.5-2.4 GB per call, past the 256 MiB Infinity Cache.
+The three kernels are timed alternately, ``--rounds`` rounds of ``--iters``
+back-to-back launches each after a warm-up round; the table gives the median
+round and the min-max spread.  AdamW should reach at least 0.9x the GB/s SGD
+reaches (same access pattern; the margin is its sqrt / divide VALU work).
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_model_parallel_amd import _native  # noqa: E402
+from distributed_model_parallel_amd.ops.optim import _SUMSQ_BLOCKS  # noqa: E402
+
+SIZES = {"resnet50": 25_557_032, "vit_b_16": 86_567_656}
+HBM_ACHIEVABLE_GBS = 6300.0  # streaming ceiling of an MI355X (8 TB/s peak)
+
+
+def time_ms(fn, iters: int) -> float:
+    """ms per call of `iters` back-to-back launches between two HIP events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--sizes", default="resnet50,vit_b_16")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        print("optim_bench: needs a GPU (a CPU timing says nothing about HBM bandwidth)", file=sys.stderr)
+        return 1
+    C = _native.require("optim_bench")
+    dev = "cuda"
+    print("| flat | elements | kernel | B/elem | ms (median) | ms (min-max) | GB/s | of 6.3 TB/s | vs SGD |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    worst = 1e9
+    for name in a.sizes.split(","):
+        n = (SIZES[name] + 7) // 8 * 8
+        g = (torch.randn(n, device=dev) * 1e-2).bfloat16()
+        master = torch.randn(n, device=dev) * 0.05
+        param = master.bfloat16()
+        m1, m2 = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        mask = (torch.arange(n // 8, device=dev) % 3 != 0).to(torch.uint8)
+        hyper = torch.zeros(4, device=dev)
+        step = torch.zeros(1, dtype=torch.int64, device=dev)
+        part = torch.zeros(1, _SUMSQ_BLOCKS, device=dev)
+        C.adamw_prepare(None, hyper, step, 0.0, 0.9, 0.999)
+        kernels = {
+            "sgd_flat_step": (20.0, lambda: C.sgd_flat_step(master, m1, g, param, 1e-3, 1e-4, 0.9, 0.0, False,
+                                                            1.0, False)),
+            "adamw_flat_step": (28.125, lambda: C.adamw_flat_step(master, m1, m2, g, param, mask, hyper, 1e-3,
+                                                                  0.9, 0.999, 1e-8, 0.05)),
+            "flat_sumsq_partials": (2.0, lambda: C.flat_sumsq_partials(g, part[0])),
+        }
+        times = {k: [] for k in kernels}
+        for r in range(a.rounds + 1):  # round 0 warms up every kernel at this size
+            for k, (_bpe, fn) in kernels.items():
+                t = time_ms(fn, a.iters)
+                if r:
+                    times[k].append(t)
+        gbs = {}
+        for k, (bpe, _fn) in kernels.items():
+            med = statistics.median(times[k])
+            gbs[k] = n * bpe / med / 1e6
+        for k, (bpe, _fn) in kernels.items():
+            med = statistics.median(times[k])
+            rel = gbs[k] / gbs["sgd_flat_step"]
+            print(f"| {name} | {n} | {k} | {bpe:g} | {med:.4f} | {min(times[k]):.4f}-{max(times[k]):.4f} | "
+                  f"{gbs[k]:.0f} | {gbs[k] / HBM_ACHIEVABLE_GBS:.2f} | {rel:.2f} |", flush=True)
+        worst = min(worst, gbs["adamw_flat_step"] / gbs["sgd_flat_step"])
+        assert torch.isfinite(master).all()
+        del g, master, param, m1, m2, mask
+    print(f"\nadamw / sgd bandwidth ratio, worst size: {worst:.3f} (target >= 0.9)")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
