@@ -253,6 +253,17 @@ void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_av
                      double beta1, double beta2, double eps, double weight_decay);
 int64_t adamw_grid_cap();  // most blocks adamw_flat_step launches (256 threads, 8 elements each)
 
+// ---- optim/fused_lars.hip ----
+void lars_norm_partials(const c10::optional<at::Tensor>& master, const at::Tensor& grad,
+                        const at::Tensor& param, const at::Tensor& items, at::Tensor& partials);
+void lars_trust(const at::Tensor& partials, const at::Tensor& tensors, at::Tensor& coef,
+                double trust_coefficient, double weight_decay, double eps);
+void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
+                    at::Tensor& param, const at::Tensor& items, const at::Tensor& coef, double lr,
+                    double momentum);
+int64_t lars_chunk_elems();   // most elements of one work item (one block of the norm / update kernels)
+int64_t lars_fold_threads();  // lanes that fold one tensor's partials in lars_trust
+
 // ---- optim/fused_sgd.hip ----
 void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mom,
                    const at::Tensor& grad, const at::Tensor& param, double lr, double wd,

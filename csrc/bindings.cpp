@@ -287,6 +287,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::call_guard<py::gil_scoped_release>());
   m.def("adamw_grid_cap", &dmp::adamw_grid_cap);
+  m.def("lars_norm_partials", &dmp::lars_norm_partials, py::arg("master"), py::arg("grad"), py::arg("param"),
+        py::arg("items"), py::arg("partials"),
+        "partials[i] = {sum g^2, sum w^2} over work item i (fixed order, no atomics)",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("lars_trust", &dmp::lars_trust, py::arg("partials"), py::arg("tensors"), py::arg("coef"),
+        py::arg("trust_coefficient"), py::arg("weight_decay"), py::arg("eps"),
+        "coef[t] = {trust ratio, weight decay, |w|, |g|} of tensor t; {1, 0, ..} for an excluded tensor",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("lars_flat_step", &dmp::lars_flat_step, py::arg("master"), py::arg("mom"), py::arg("grad"),
+        py::arg("param"), py::arg("items"), py::arg("coef"), py::arg("lr"), py::arg("momentum"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("lars_chunk_elems", &dmp::lars_chunk_elems);
+  m.def("lars_fold_threads", &dmp::lars_fold_threads);
 
   // ---- coalesced movement ----
   m.def("multi_copy", &dmp::multi_copy,

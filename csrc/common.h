@@ -57,6 +57,31 @@ template <> struct Vec16<__bf16> {
   }
 };
 
+// ---- 8 consecutive elements of bf16 (one 16-B access) or fp32 (two), as f32 ----
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, float (&v)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    Vec16<__bf16>::load(reinterpret_cast<const __bf16*>(p), v);
+  } else {
+    float a[4], b[4];
+    Vec16<float>::load(reinterpret_cast<const float*>(p), a);
+    Vec16<float>::load(reinterpret_cast<const float*>(p) + 4, b);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float (&v)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    Vec16<__bf16>::store(reinterpret_cast<__bf16*>(p), v);
+  } else {
+    float a[4] = {v[0], v[1], v[2], v[3]}, b[4] = {v[4], v[5], v[6], v[7]};
+    Vec16<float>::store(reinterpret_cast<float*>(p), a);
+    Vec16<float>::store(reinterpret_cast<float*>(p) + 4, b);
+  }
+}
+
 // Streaming (non-temporal) 16-B accesses for tensors touched exactly once per
 // pass and far larger than the 256 MB Infinity Cache (BN apply passes over
 // 0.4-1.6 GB activations): the nt policy keeps them from evicting reused lines.

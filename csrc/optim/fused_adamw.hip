@@ -32,30 +32,6 @@ constexpr int kMaxBlocks = 256 * 8;  // grid cap of adamw_flat_step (as sgd_flat
 // hyper[] slots (fp32, device)
 constexpr int kBc1 = 0, kBc2 = 1, kNorm = 2, kClip = 3, kHyper = 4;
 
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&v)[8]) {
-  if constexpr (sizeof(T) == 2) {
-    Vec16<__bf16>::load(reinterpret_cast<const __bf16*>(p), v);
-  } else {
-    float a[4], b[4];
-    Vec16<float>::load(reinterpret_cast<const float*>(p), a);
-    Vec16<float>::load(reinterpret_cast<const float*>(p) + 4, b);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void store8(T* p, const float (&v)[8]) {
-  if constexpr (sizeof(T) == 2) {
-    Vec16<__bf16>::store(reinterpret_cast<__bf16*>(p), v);
-  } else {
-    float a[4] = {v[0], v[1], v[2], v[3]}, b[4] = {v[4], v[5], v[6], v[7]};
-    Vec16<float>::store(reinterpret_cast<float*>(p), a);
-    Vec16<float>::store(reinterpret_cast<float*>(p) + 4, b);
-  }
-}
-
 // Block b sums the squares of its grid-stride share of the vectors and writes
 // out[b]; block 0 also zeroes the slots [gridDim.x, nslots) no block owns.
 template <typename G>

@@ -1,25 +1,27 @@
-"""Flat optimizers: torch.optim.SGD / torch.optim.AdamW semantics, one HIP
-launch per dtype group.
+"""Flat optimizers: torch.optim.SGD / torch.optim.AdamW semantics and LARS, a
+constant number of HIP launches per dtype group.
 
-``FlatSGD`` / ``FlatAdamW`` work on the flat parameter / gradient buffers of
-``DistributedDataParallel(..., flat_parameters=True)``: gradients there are
-already RCCL-averaged bucket views, parameters are views of a flat buffer with
-the same layout, so the update of all 161 ResNet-50 tensors is a single
-vectorised pass (``csrc/optim/fused_sgd.hip``, ``csrc/optim/fused_adamw.hip``).
-``MasterSGD`` / ``MasterAdamW`` build the same kind of flat buffers for any
-parameter list.  bf16 parameter groups keep an fp32 master copy and fp32
-optimizer state inside the optimizer; the kernel writes the bf16 working
-weights back in the same pass.
+``FlatSGD`` / ``FlatAdamW`` / ``FlatLARS`` work on the flat parameter /
+gradient buffers of ``DistributedDataParallel(..., flat_parameters=True)``:
+gradients there are already RCCL-averaged bucket views, parameters are views
+of a flat buffer with the same layout, so the update of all 161 ResNet-50
+tensors is a single vectorised pass (``csrc/optim/fused_sgd.hip``,
+``csrc/optim/fused_adamw.hip``, ``csrc/optim/fused_lars.hip``).
+``MasterSGD`` / ``MasterAdamW`` / ``MasterLARS`` build the same kind of flat
+buffers for any parameter list.  bf16 parameter groups keep an fp32 master copy
+and fp32 optimizer state inside the optimizer; the kernel writes the bf16
+working weights back in the same pass.
 
-The four classes are a layout (``_DDPLayout`` / ``_ListLayout``: where the
+The six classes are a layout (``_DDPLayout`` / ``_ListLayout``: where the
 flats come from, how state follows a bucket rebuild, checkpoint format) times
-an update rule (``_SGDRule`` / ``_AdamWRule``), on the shared ``_FlatOptimizer``
-step.
+an update rule (``_SGDRule`` / ``_AdamWRule`` / ``_LARSRule``), on the shared
+``_FlatOptimizer`` step.
 
 Reference parity: SGD(lr, momentum 0.9, weight_decay 1e-4) at
 ``model_parallel.py:105`` / ``data_parallel.py:90``.  AdamW
 with decoupled decay off for biases / norm weights and global-norm clipping is
-what every ViT recipe trains with.
+what every ViT recipe trains with; LARS (per-tensor trust ratios from a
+segmented norm over the flats) is what large-batch ResNet recipes train with.
 """
 from __future__ import annotations
 
@@ -473,8 +475,130 @@ class _AdamWRule:
             ds["step"].fill_(int(n))
 
 
+# coef[] columns written by lars_trust (csrc/optim/fused_lars.hip): trust ratio, weight decay, |w|, |g|
+_TRUST, _COEF_COLS = 0, 4
+
+
+class _LARSRule:
+    """LARS (You et al. 2017) with momentum: per tensor
+    ``trust = eta |w| / (|g| + wd |w| + eps)`` (1 where ``|w|`` or ``|g|`` is
+    exactly 0), ``d = trust (g + wd w)``, ``m <- mu m + d``, ``w <- w - lr m``.
+    With ``exclude_1d`` parameters with ``ndim <= 1`` (biases, BatchNorm /
+    LayerNorm weights) get ``trust = 1`` and no weight decay: ``d = g``.
+
+    The norms are taken over the fp32 masters (the fp32 parameters where there
+    is no master) and the averaged gradient, per tensor, by a segmented
+    reduction over the flats: three launches per dtype group whatever the number
+    of tensors.  Norms and trust ratios stay on the device, so ``step()`` never
+    syncs the host and a step captured into a hipGraph stays correct on replay;
+    ``lr`` is a host scalar outside the momentum, as in the SGD classes (the
+    schedules write ``param_groups[0]['lr']``).  Gradients are equal on every
+    rank after the all-reduce and the norms are per tensor, so LARS needs no
+    communication of its own and works per stage in a pipeline.
+    """
+
+    KIND = "lars"
+    STATE_KEYS = ("momentum",)
+
+    def _lars_defaults(self, lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d) -> dict:
+        if lr < 0 or momentum < 0 or weight_decay < 0 or trust_coefficient <= 0 or eps < 0:
+            raise ValueError("%s: lr, momentum, weight_decay and eps must not be negative, "
+                             "trust_coefficient must be positive" % self._name())
+        self.exclude_1d = bool(exclude_1d)
+        self._plans: List[dict] = []
+        self._plan_key = None
+        self._stepped = False
+        return dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                    trust_coefficient=trust_coefficient, eps=eps)
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("%s supports one param group (adaptation is switched per parameter by "
+                             "exclude_1d)" % self._name())
+        super().add_param_group(param_group)
+
+    def _lars_plans(self, groups: List[dict]) -> List[dict]:
+        """Per group, the work items of the segmented reduction and the update,
+        built on the host once per layout and kept on the group's device:
+
+        ``items``    int32 [I, 3]: first vector, vector count, tensor -- every
+                     parameter's slot cut into pieces of at most
+                     ``lars_chunk_elems()`` elements, none across a boundary
+        ``tensors``  int32 [T, 3]: first item, item count, adapted?  (``_slots`` order)
+        ``partials`` fp32 [I, 2], ``coef`` fp32 [T, 4]: the kernels' outputs
+        """
+        key = (self._layout_id(), len(groups))
+        if self._plan_key == key:
+            return self._plans
+        plans = []
+        for gi, st in enumerate(groups):
+            dev = st["param"].device
+            # vectors per work item (the CPU path works on `spans`: one item per tensor there)
+            chunk = _native.require(self._name()).lars_chunk_elems() // 8 if dev.type == "cuda" else 1 << 30
+            items, tensors, spans = [], [], []
+            nitems = 0
+            for t, (p, off) in enumerate(self._slots(gi)):
+                if off % 8:
+                    raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
+                                       % (self._name(), off))
+                nvec = (p.numel() + 7) // 8
+                adapted = not self.exclude_1d or p.dim() > 1
+                first = torch.arange(off // 8, off // 8 + nvec, chunk, dtype=torch.int32)
+                count = torch.clamp(off // 8 + nvec - first, max=chunk)
+                items.append(torch.stack([first, count, torch.full_like(first, t)], dim=1))
+                tensors.append((nitems, first.numel(), int(adapted)))
+                spans.append((off, nvec * 8, adapted))
+                nitems += first.numel()
+            items = torch.cat(items) if items else torch.zeros(0, 3, dtype=torch.int32)
+            tensors = torch.tensor(tensors, dtype=torch.int32).reshape(-1, 3)
+            plans.append({"items": items.contiguous().to(dev), "tensors": tensors.to(dev), "spans": spans,
+                          "adapted": tensors[:, 2].bool().to(dev),
+                          "partials": torch.zeros(nitems, 2, dtype=torch.float32, device=dev),
+                          "coef": torch.zeros(len(spans), _COEF_COLS, dtype=torch.float32, device=dev)})
+        self._plans, self._plan_key = plans, key
+        return plans
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        if not groups:
+            return
+        for st, plan in zip(groups, self._lars_plans(groups)):
+            pflat, master = st["param"], st.get("master")
+            if pflat.is_cuda:
+                C = _native.require(self._name())
+                C.lars_norm_partials(master, st["grad"], pflat, plan["items"], plan["partials"])
+                C.lars_trust(plan["partials"], plan["tensors"], plan["coef"], float(g["trust_coefficient"]),
+                             float(g["weight_decay"]), float(g["eps"]))
+                C.lars_flat_step(master, st["momentum"], st["grad"], pflat, plan["items"], plan["coef"],
+                                 float(g["lr"]), float(g["momentum"]))
+            else:
+                _lars_reference(master, st["momentum"], st["grad"], pflat, plan["spans"], plan["coef"], g)
+        self._stepped = True
+
+    @property
+    def last_trust_ratios(self) -> Optional[List[torch.Tensor]]:
+        """The last step's trust ratios: one fp32 device tensor per dtype group,
+        one value per parameter in ``_slots(group)`` order, 1 for an excluded
+        parameter (reading it is the caller's sync); ``None`` before a step."""
+        if not self._stepped or self._plan_key is None:
+            return None
+        return [plan["coef"][:, _TRUST] for plan in self._plans]
+
+    def last_trust_range(self) -> Optional[Tuple[float, float]]:
+        """(min, max) of the last step's trust ratios over the adapted
+        parameters (this reads the device: once per epoch in the trainer)."""
+        ratios = self.last_trust_ratios
+        if ratios is None:
+            return None
+        vals = [r[plan["adapted"]] for r, plan in zip(ratios, self._plans)]
+        vals = torch.cat([v.float().cpu() for v in vals]) if vals else torch.zeros(0)
+        if vals.numel() == 0:
+            return None
+        return float(vals.min()), float(vals.max())
+
+
 # --------------------------------------------------------------------------- #
-# the four optimizers
+# the six optimizers
 # --------------------------------------------------------------------------- #
 class FlatSGD(_SGDRule, _DDPLayout, _FlatOptimizer):
     def __init__(self, ddp, lr: float, momentum: float = 0.0, dampening: float = 0.0,
@@ -544,20 +668,55 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
         self._clip_devices(self._groups)
 
 
+class FlatLARS(_LARSRule, _DDPLayout, _FlatOptimizer):
+    """LARS with momentum on the DDP flat buffers (twin of :class:`FlatSGD`), the
+    optimizer of large-batch ResNet recipes.  ``exclude_1d`` keeps parameters
+    with ``ndim <= 1`` (biases, BatchNorm / LayerNorm weights) on plain momentum
+    SGD without weight decay."""
+
+    def __init__(self, ddp, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
+                 trust_coefficient: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True,
+                 master_weights: bool = True):
+        defaults = self._lars_defaults(lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d)
+        super().__init__(list(ddp._params), defaults)
+        self._init_layout(ddp, master_weights)
+
+
+class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
+    """:class:`FlatLARS` for ANY parameter list (twin of :class:`MasterSGD`)."""
+
+    def __init__(self, params, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
+                 trust_coefficient: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True,
+                 master_weights: bool = True):
+        defaults = self._lars_defaults(lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d)
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            if len(params) > 1:
+                raise ValueError("MasterLARS supports one param group (adaptation is switched per "
+                                 "parameter by exclude_1d)")
+            params = list(params[0]["params"])
+        params = [p for p in params if p.requires_grad]
+        super().__init__(params, defaults)
+        self._init_layout(params, master_weights)
+
+
 def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 0.9,
                     weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                    clip_grad_norm: float = 0.0):
-    """The trainer's optimizer: ``kind`` sgd | adamw; ``flat`` picks the DDP-flat
-    class (``target`` is the DDP wrapper) over the parameter-list one."""
+                    clip_grad_norm: float = 0.0, trust_coefficient: float = 1e-3):
+    """The trainer's optimizer: ``kind`` sgd | adamw | lars; ``flat`` picks the
+    DDP-flat class (``target`` is the DDP wrapper) over the parameter-list one."""
+    if kind in ("sgd", "lars") and clip_grad_norm:
+        raise ValueError("gradient clipping needs optimizer='adamw'")
     if kind == "sgd":
-        if clip_grad_norm:
-            raise ValueError("gradient clipping needs optimizer='adamw'")
         return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay)
     if kind == "adamw":
         return (FlatAdamW if flat else MasterAdamW)(target, lr=lr, betas=betas, eps=eps,
                                                     weight_decay=weight_decay,
                                                     max_grad_norm=clip_grad_norm or None)
-    raise ValueError(f"unknown optimizer {kind!r} (sgd | adamw)")
+    if kind == "lars":
+        return (FlatLARS if flat else MasterLARS)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                                  trust_coefficient=trust_coefficient, eps=eps)
+    raise ValueError(f"unknown optimizer {kind!r} (sgd | adamw | lars)")
 
 
 # --------------------------------------------------------------------------- #
@@ -575,6 +734,35 @@ def _sgd_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: torc
             mom.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
         d = d + g["momentum"] * mom if g["nesterov"] else mom
     w.add_(d.to(w.dtype), alpha=-g["lr"])
+    if master is not None:
+        param.copy_(master.to(param.dtype))
+
+
+def _lars_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: torch.Tensor,
+                    param: torch.Tensor, spans, coef: torch.Tensor, g: dict) -> None:
+    """PyTorch implementation of the three LARS kernels, fp32 like them (norms
+    and trust ratio in double).  ``spans``: (offset, padded length, adapted?) per
+    tensor; ``coef`` [T, 4] receives {trust, weight decay, |w|, |g|}."""
+    w = master if master is not None else param
+    wf = w if w.dtype == torch.float32 else w.float()
+    eta, wd, eps = float(g["trust_coefficient"]), float(g["weight_decay"]), float(g["eps"])
+    for t, (off, n, adapted) in enumerate(spans):
+        ws, ms = wf.narrow(0, off, n), mom.narrow(0, off, n)
+        gs = grad.narrow(0, off, n).float()
+        wn, gn = ws.double().norm(), gs.double().norm()
+        trust, decay = 1.0, 0.0
+        if adapted:
+            decay = wd
+            if float(wn) != 0.0 and float(gn) != 0.0:
+                trust = float(eta * wn / (gn + wd * wn + eps))
+        coef[t] = torch.tensor([trust, decay, float(wn), float(gn)], dtype=torch.float32)
+        d = gs + decay * ws if decay else gs
+        if trust != 1.0:
+            d = d * torch.tensor(trust, dtype=torch.float32)
+        ms.mul_(g["momentum"]).add_(d)
+        ws.sub_(ms, alpha=g["lr"])
+    if wf is not w:
+        w.copy_(wf.to(w.dtype))
     if master is not None:
         param.copy_(master.to(param.dtype))
 

@@ -31,6 +31,9 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 
+TRUST_COEFFICIENT = 1e-3  # --trust-coefficient when the flag is absent
+
+
 def _betas(text: str):
     try:
         b1, b2 = (float(v) for v in text.split(","))
@@ -45,6 +48,12 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--clip-grad-norm must not be negative")
     if args.clip_grad_norm and args.optimizer != "adamw":
         parser.error("--clip-grad-norm needs --optimizer adamw")
+    if args.trust_coefficient is not None and args.optimizer != "lars":
+        parser.error("--trust-coefficient needs --optimizer lars")
+    if args.trust_coefficient is None:
+        args.trust_coefficient = TRUST_COEFFICIENT
+    if args.trust_coefficient <= 0:
+        parser.error("--trust-coefficient must be positive")
     world = args.world_size or int(os.environ.get("WORLD_SIZE", "1"))
     if args.clip_grad_norm and args.parallel == "pipe" and world > 1:
         parser.error("--clip-grad-norm with --parallel pipe at world size > 1 is not supported "
@@ -53,9 +62,22 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
 
 def _optimizer(args, target, flat: bool):
     from ..ops.optim import build_optimizer
+    trust = TRUST_COEFFICIENT if args.trust_coefficient is None else args.trust_coefficient
     return build_optimizer(args.optimizer, target, flat, lr=args.lr, momentum=args.momentum,
                            weight_decay=args.weight_decay, betas=args.betas, eps=args.eps,
-                           clip_grad_norm=args.clip_grad_norm)
+                           clip_grad_norm=args.clip_grad_norm, trust_coefficient=trust)
+
+
+def _optimizer_log(args, opt) -> dict:
+    """What the epoch log line says about the optimizer's last step (one device read per epoch)."""
+    extra = {}
+    if args.clip_grad_norm and opt.last_grad_norm is not None:
+        extra["grad_norm"] = float(opt.last_grad_norm)
+    if args.optimizer == "lars":
+        span = opt.last_trust_range()  # over the adapted tensors
+        if span is not None:
+            extra["trust_min"], extra["trust_max"] = span
+    return extra
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -73,10 +95,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-j", "--workers", default=4, type=int)
     p.add_argument("--wd", "--weight-decay", default=1e-4, type=float, dest="weight_decay")
     p.add_argument("--momentum", default=0.9, type=float)
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
-                   help="adamw: decoupled weight decay (off for biases / norm weights), e.g. --lr 1e-3 --wd 0.05")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lars"],
+                   help="adamw: decoupled weight decay (off for biases / norm weights), e.g. --lr 1e-3 --wd 0.05; "
+                        "lars: momentum SGD with per-tensor trust ratios (biases / norm weights excluded), "
+                        "for large batches")
     p.add_argument("--betas", default=(0.9, 0.999), type=_betas, metavar="B1,B2", help="--optimizer adamw")
-    p.add_argument("--eps", default=1e-8, type=float, help="--optimizer adamw")
+    p.add_argument("--eps", default=1e-8, type=float, help="--optimizer adamw / lars")
+    p.add_argument("--trust-coefficient", default=None, type=float, metavar="ETA",
+                   help=f"--optimizer lars: trust ratio = ETA |w| / (|g| + wd |w| + eps) (default {TRUST_COEFFICIENT})")
     p.add_argument("--clip-grad-norm", default=0.0, type=float, metavar="X",
                    help="--optimizer adamw: clip the global gradient norm to X (0 = off)")
     p.add_argument("-r", "--resume", action="store_true")
@@ -236,9 +262,7 @@ def run_data_parallel(args, env) -> None:
         if env.is_main and va > best:
             best = va
             save_checkpoint(args.checkpoint, net, opt, sched, epoch, best)
-        extra = {}
-        if args.clip_grad_norm and opt.last_grad_norm is not None:
-            extra["grad_norm"] = float(opt.last_grad_norm)  # the epoch's last step; one read per epoch
+        extra = _optimizer_log(args, opt)  # the epoch's last step; one read per epoch
         logger.log(epoch, loss_train=lm.avg, acc1_train=am.avg, loss_val=vl, acc1_val=va,
                    time_per_batch=step_s + data_s, time_load_perbatch=data_s,
                    images_per_sec=(args.batch_size * max(1, env.world_size if args.parallel == "ddp" else 1))
@@ -370,9 +394,7 @@ def run_pipeline(args, env) -> None:
         save_checkpoint(stage_checkpoint_path(args.checkpoint, env.rank), pipe.module, opt, sched, epoch,
                         all_ranks=True)
         if env.rank == 0:
-            extra = {}
-            if args.clip_grad_norm and opt.last_grad_norm is not None:
-                extra["grad_norm"] = float(opt.last_grad_norm)
+            extra = _optimizer_log(args, opt)
             logger.log(epoch, loss_train=loss_s / max(n_train, 1), acc1_train=acc_s / max(n_train, 1),
                        loss_val=vl / max(n_val, 1), acc1_val=va / max(n_val, 1),
                        time_per_batch=tot_t / max(n_train, 1), time_load_perbatch=tot_d / max(n_train, 1),

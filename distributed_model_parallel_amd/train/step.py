@@ -40,10 +40,11 @@ class StepConfig:
     lr: float = 0.1
     momentum: float = 0.9
     weight_decay: float = 1e-4
-    optimizer: str = "sgd"          # sgd | adamw (ops/optim.py)
+    optimizer: str = "sgd"          # sgd | adamw | lars (ops/optim.py)
     betas: tuple = (0.9, 0.999)     # optimizer == "adamw"
-    eps: float = 1e-8               # optimizer == "adamw"
+    eps: float = 1e-8               # optimizer == "adamw" / "lars"
     clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
+    trust_coefficient: float = 1e-3  # optimizer == "lars"
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -83,7 +84,7 @@ def synthetic_batch(cfg: StepConfig, device: torch.device, generator_seed: int =
 def _optimizer(cfg: StepConfig, target, flat: bool) -> torch.optim.Optimizer:
     return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
                            weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
-                           clip_grad_norm=cfg.clip_grad_norm)
+                           clip_grad_norm=cfg.clip_grad_norm, trust_coefficient=cfg.trust_coefficient)
 
 
 def build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:

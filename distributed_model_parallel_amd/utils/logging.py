@@ -20,10 +20,11 @@ from typing import Any, Dict, Optional
 def reference_line(epoch: int, rec: Dict[str, Any]) -> str:
     """``step:E  loss_train:..  acc1_train:..  loss_val:..  acc1_val:..[  time_per_batch:..
     time_load_perbatch:..]`` exactly in the reference's key order; ``grad_norm`` follows
-    when the run clips gradients (the reference has no such field)."""
+    when the run clips gradients, ``trust_min`` / ``trust_max`` under LARS (the reference
+    has no such fields)."""
     parts = [f"step:{epoch}"]
     for k in ("loss_train", "acc1_train", "loss_val", "acc1_val", "time_per_batch",
-              "time_load_perbatch", "grad_norm"):
+              "time_load_perbatch", "grad_norm", "trust_min", "trust_max"):
         if k in rec and rec[k] is not None:
             parts.append(f"{k}:{rec[k]}")
     return "  ".join(parts)

@@ -7,13 +7,20 @@
 * ``adamw_flat_step`` bf16 + master, per-vector decay mask: reads g(2) w(4)
   m(4) v(4), writes m(4) v(4) w(4) p(2) = 28 B per element (+ 0.125 B mask);
 * ``flat_sumsq_partials`` bf16 gradient: 2 B per element;
+* the three LARS kernels: ``lars_norm_partials`` reads g(2) w(4) = 6 B per
+  element, ``lars_trust`` reads the per-item partials (launch-bound),
+  ``lars_flat_step`` moves what the SGD kernel moves, 20 B per element;
 
-on flats of ResNet-50 size (25.6 M elements) and ViT-B/16 size (86.6 M).  Both
+on the flats of ResNet-50 (25.6 M elements) and ViT-B/16 (86.6 M), laid out
+tensor by tensor as the optimizers lay them out (every slot padded to 8
+elements), so the LARS plan has the models' real tensor boundaries.  The
 update kernels stream 0.5-2.4 GB per call, past the 256 MiB Infinity Cache.
-The three kernels are timed alternately, ``--rounds`` rounds of ``--iters``
+The kernels are timed alternately, ``--rounds`` rounds of ``--iters``
 back-to-back launches each after a warm-up round; the table gives the median
 round and the min-max spread.  AdamW should reach at least 0.9x the GB/s SGD
-reaches (same access pattern; the margin is its sqrt / divide VALU work).
+reaches (same access pattern; the margin is its sqrt / divide VALU work); a
+LARS step (its three kernels) should take about 1.3x the SGD kernel's time
+(26 B against 20 B per element, plus two short launches).
 """
 import argparse
 import os
@@ -24,10 +31,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_model_parallel_amd import _native  # noqa: E402
-from distributed_model_parallel_amd.ops.optim import _SUMSQ_BLOCKS  # noqa: E402
+from distributed_model_parallel_amd.ops.optim import _SUMSQ_BLOCKS, MasterLARS  # noqa: E402
 
 SIZES = {"resnet50": 25_557_032, "vit_b_16": 86_567_656}
 HBM_ACHIEVABLE_GBS = 6300.0  # streaming ceiling of an MI355X (8 TB/s peak)
+LARS = ("lars_norm_partials", "lars_trust", "lars_flat_step")
 
 
 def time_ms(fn, iters: int) -> float:
@@ -39,6 +47,21 @@ def time_ms(fn, iters: int) -> float:
     b.record()
     b.synchronize()
     return a.elapsed_time(b) / iters
+
+
+def model_flat(name: str, dev: str):
+    """The model's parameters as bf16 tensors in one flat, under a MasterLARS
+    that has taken one step (so its plan is on the device)."""
+    from distributed_model_parallel_amd.models import build_model
+    with torch.device("meta"):
+        shapes = [tuple(p.shape) for p in build_model(name).parameters()]
+    assert sum(torch.Size(s).numel() for s in shapes) == SIZES[name], name
+    params = [torch.nn.Parameter((torch.randn(s, device=dev) * 0.05).bfloat16()) for s in shapes]
+    opt = MasterLARS(params, lr=1e-3, momentum=0.9, weight_decay=1e-4)
+    opt._groups[0]["grad"].copy_((torch.randn(opt._groups[0]["grad"].numel(), device=dev) * 1e-2)
+                                 * (opt._groups[0]["param"] != 0))  # the slots' padding stays zero
+    opt.step()
+    return opt, len(shapes)
 
 
 def main(argv=None) -> int:
@@ -54,24 +77,32 @@ def main(argv=None) -> int:
     dev = "cuda"
     print("| flat | elements | kernel | B/elem | ms (median) | ms (min-max) | GB/s | of 6.3 TB/s | vs SGD |")
     print("|---|---|---|---|---|---|---|---|---|")
-    worst = 1e9
+    worst, notes = 1e9, []
     for name in a.sizes.split(","):
-        n = (SIZES[name] + 7) // 8 * 8
-        g = (torch.randn(n, device=dev) * 1e-2).bfloat16()
-        master = torch.randn(n, device=dev) * 0.05
-        param = master.bfloat16()
-        m1, m2 = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        opt, ntensors = model_flat(name, dev)
+        st, plan = opt._groups[0], opt._plans[0]
+        g, master, param, m1 = st["grad"], st["master"], st["param"], st["momentum"]
+        n = param.numel()
+        m1.zero_()
+        # every rule keeps its own state: an exp_avg fed with SGD's momentum (10 g) over sqrt(exp_avg_sq)
+        # makes steps that grow with the weights, and hundreds of timed launches then overflow them
+        m2, ma, ml = (torch.zeros(n, device=dev) for _ in range(3))
         mask = (torch.arange(n // 8, device=dev) % 3 != 0).to(torch.uint8)
         hyper = torch.zeros(4, device=dev)
         step = torch.zeros(1, dtype=torch.int64, device=dev)
         part = torch.zeros(1, _SUMSQ_BLOCKS, device=dev)
+        items, tensors, partials, coef = plan["items"], plan["tensors"], plan["partials"], plan["coef"]
         C.adamw_prepare(None, hyper, step, 0.0, 0.9, 0.999)
         kernels = {
             "sgd_flat_step": (20.0, lambda: C.sgd_flat_step(master, m1, g, param, 1e-3, 1e-4, 0.9, 0.0, False,
                                                             1.0, False)),
-            "adamw_flat_step": (28.125, lambda: C.adamw_flat_step(master, m1, m2, g, param, mask, hyper, 1e-3,
+            "adamw_flat_step": (28.125, lambda: C.adamw_flat_step(master, ma, m2, g, param, mask, hyper, 1e-3,
                                                                   0.9, 0.999, 1e-8, 0.05)),
             "flat_sumsq_partials": (2.0, lambda: C.flat_sumsq_partials(g, part[0])),
+            "lars_norm_partials": (6.0, lambda: C.lars_norm_partials(master, g, param, items, partials)),
+            "lars_trust": ((partials.numel() + tensors.numel() + coef.numel()) * 4 / n,
+                           lambda: C.lars_trust(partials, tensors, coef, 1e-3, 1e-4, 1e-8)),
+            "lars_flat_step": (20.0, lambda: C.lars_flat_step(master, ml, g, param, items, coef, 1e-3, 0.9)),
         }
         times = {k: [] for k in kernels}
         for r in range(a.rounds + 1):  # round 0 warms up every kernel at this size
@@ -79,19 +110,22 @@ def main(argv=None) -> int:
                 t = time_ms(fn, a.iters)
                 if r:
                     times[k].append(t)
-        gbs = {}
+        gbs, med = {}, {}
         for k, (bpe, _fn) in kernels.items():
-            med = statistics.median(times[k])
-            gbs[k] = n * bpe / med / 1e6
+            med[k] = statistics.median(times[k])
+            gbs[k] = n * bpe / med[k] / 1e6
         for k, (bpe, _fn) in kernels.items():
-            med = statistics.median(times[k])
             rel = gbs[k] / gbs["sgd_flat_step"]
-            print(f"| {name} | {n} | {k} | {bpe:g} | {med:.4f} | {min(times[k]):.4f}-{max(times[k]):.4f} | "
+            print(f"| {name} | {n} | {k} | {bpe:.4g} | {med[k]:.4f} | {min(times[k]):.4f}-{max(times[k]):.4f} | "
                   f"{gbs[k]:.0f} | {gbs[k] / HBM_ACHIEVABLE_GBS:.2f} | {rel:.2f} |", flush=True)
         worst = min(worst, gbs["adamw_flat_step"] / gbs["sgd_flat_step"])
+        lars = sum(med[k] for k in LARS)
+        notes.append(f"{name}: {ntensors} tensors, {items.shape[0]} work items; lars (norm + trust + step) "
+                     f"{lars:.4f} ms = {lars / med['sgd_flat_step']:.3f} x sgd_flat_step")
         assert torch.isfinite(master).all()
-        del g, master, param, m1, m2, mask
+        del opt, st, plan, g, master, param, m1, m2, ma, ml, mask, kernels
     print(f"\nadamw / sgd bandwidth ratio, worst size: {worst:.3f} (target >= 0.9)")
+    print("\n".join(notes) + "\n(expected from the traffic: about 1.3)")
     return 0
 
 
