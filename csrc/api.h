@@ -174,6 +174,9 @@ at::Tensor wgrad3x3(const at::Tensor& dy, const at::Tensor& x, int64_t stride);
 bool wgrad3x3_supported(int64_t C, int64_t H, int64_t W, int64_t stride);
 void set_wgrad3x3_waves(int64_t nw);
 
+// ---- data/batch_mix.hip ----
+at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, const std::vector<int64_t>& box);
+
 // ---- gemm/gemm_xl.hip (NT) ----
 at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& mode,
                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& aux,
@@ -228,10 +231,11 @@ std::vector<at::Tensor> gelu_bwd_bias_grad(const at::Tensor& dy, const at::Tenso
 // ---- loss/cross_entropy.hip ----
 std::vector<at::Tensor> cross_entropy_fwd(const at::Tensor& x, const at::Tensor& target,
                                           int64_t ignore_index, double scale,
-                                          const c10::optional<at::Tensor>& acc);
+                                          const c10::optional<at::Tensor>& acc, double label_smoothing,
+                                          const c10::optional<at::Tensor>& target_b, double lam);
 at::Tensor cross_entropy_bwd(const at::Tensor& grad, const at::Tensor& x, const at::Tensor& target,
-                             const at::Tensor& lse, const at::Tensor& stats, int64_t ignore_index);
-
+                             const at::Tensor& lse, const at::Tensor& stats, int64_t ignore_index,
+                             double label_smoothing, const c10::optional<at::Tensor>& target_b, double lam);
 // ---- norm/layernorm.hip ----
 std::vector<at::Tensor> layernorm_forward(const at::Tensor& x, const c10::optional<at::Tensor>& w,
                                           const c10::optional<at::Tensor>& b, int64_t D,

@@ -52,10 +52,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.def("cross_entropy_fwd", &dmp::cross_entropy_fwd, py::arg("x"), py::arg("target"),
         py::arg("ignore_index") = -100, py::arg("scale") = 1.0, py::arg("acc") = py::none(),
-        "scale * mean softmax cross-entropy; acc (fp64 [3]) += (loss, top-1 correct, top-5 correct)",
+        py::arg("label_smoothing") = 0.0, py::arg("target_b") = py::none(), py::arg("lam") = 1.0,
+        "scale * mean softmax cross-entropy; acc (fp64 [3]) += (loss, top-1 correct, top-5 correct); "
+        "label_smoothing and a second label target_b weighted 1 - lam give the soft-target loss",
         py::call_guard<py::gil_scoped_release>());
   m.def("cross_entropy_bwd", &dmp::cross_entropy_bwd, py::arg("grad"), py::arg("x"), py::arg("target"),
-        py::arg("lse"), py::arg("stats"), py::arg("ignore_index") = -100,
+        py::arg("lse"), py::arg("stats"), py::arg("ignore_index") = -100, py::arg("label_smoothing") = 0.0,
+        py::arg("target_b") = py::none(), py::arg("lam") = 1.0, py::call_guard<py::gil_scoped_release>());
+  m.def("batch_mix", &dmp::batch_mix, py::arg("x"), py::arg("perm"), py::arg("lam"),
+        py::arg("box") = std::vector<int64_t>{},
+        "mixup (empty box): lam * x[i] + (1 - lam) * x[perm[i]]; CutMix (box = [y0, y1, x0, x1]): "
+        "x[perm[i]] inside the box, x[i] outside; channels-last bf16 / fp32, out of place",
         py::call_guard<py::gil_scoped_release>());
   m.def("gemm_nt_bnbwd", &dmp::gemm_nt_bnbwd, py::arg("A"), py::arg("B"), py::arg("residual"),
         py::arg("bn_x"), py::arg("bn_y"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),

@@ -264,7 +264,12 @@ class Pipeline:
                  partition=None, balance: str = "flops",
                  device: Optional[torch.device] = None, dtype: torch.dtype = torch.float32,
                  channels_last: bool = False, static_batch: Optional[int] = None,
-                 fail_fast: bool = True, graphs: bool = False, kernel_grad_accum: bool = True):
+                 fail_fast: bool = True, graphs: bool = False, kernel_grad_accum: bool = True,
+                 label_smoothing: float = 0.0):
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        if label_smoothing and loss_fn is not None:
+            raise ValueError("label_smoothing applies to the default loss only: smooth inside the custom loss_fn")
         if schedule not in ("naive", "gpipe", "1f1b"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if loss_on not in ("last", "first"):
@@ -279,6 +284,7 @@ class Pipeline:
         if loss_fn is None:
             from ..ops.loss import cross_entropy as loss_fn  # fused HIP kernel on GPU
         self.loss_fn = loss_fn
+        self.label_smoothing = float(label_smoothing)  # training micro-batches only; eval_step stays plain
         self.loss_on = loss_on if self.world > 1 else "last"
         self.device = torch.device(device) if device is not None else comm.device
         self.dtype = dtype
@@ -468,15 +474,22 @@ class Pipeline:
         when the stage uses the default loss on the GPU; else None."""
         from ..ops import loss as L
         if self.loss_fn is L.cross_entropy and stats.is_cuda and L._native_ce_ok(y, t):
-            return L.cross_entropy_with_stats(y, t, 1.0 / self.micro_batches, stats)
+            return L.cross_entropy_with_stats(y, t, 1.0 / self.micro_batches, stats,
+                                              label_smoothing=self.label_smoothing)
         return None
+
+    def _train_loss(self, logits: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """The training loss of one micro-batch (label smoothing: default loss only)."""
+        if self.label_smoothing:
+            return self.loss_fn(logits, t, label_smoothing=self.label_smoothing)
+        return self.loss_fn(logits, t)
 
     def _loss_and_stats(self, y: torch.Tensor, t: torch.Tensor, stats: torch.Tensor) -> torch.Tensor:
         fused = self._fused_loss(y, t, stats)
         if fused is not None:
             return fused
         logits = y.float()
-        loss = self.loss_fn(logits, t) / self.micro_batches
+        loss = self._train_loss(logits, t) / self.micro_batches
         with torch.no_grad():
             c1, c5 = _topk_correct(logits, t)
             stats[0] += loss.detach().double()
@@ -827,7 +840,7 @@ class _StageGraphs:
         if fused is not None:
             return fused
         logits = y.float()
-        loss = pipe.loss_fn(logits, self.targets[k]) / pipe.micro_batches
+        loss = pipe._train_loss(logits, self.targets[k]) / pipe.micro_batches
         with torch.no_grad():
             c1, c5 = _topk_correct(logits, self.targets[k])
             self.stats[0] += loss.detach().double()

@@ -54,6 +54,20 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
         args.trust_coefficient = TRUST_COEFFICIENT
     if args.trust_coefficient <= 0:
         parser.error("--trust-coefficient must be positive")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        parser.error("--label-smoothing must be in [0, 1)")
+    if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
+        parser.error("--mixup-alpha / --cutmix-alpha must not be negative")
+    mixing = args.mixup_alpha > 0 or args.cutmix_alpha > 0
+    if args.mix_prob is not None and not mixing:
+        parser.error("--mix-prob needs --mixup-alpha or --cutmix-alpha")
+    if args.mix_prob is None:
+        args.mix_prob = 1.0
+    if not 0.0 <= args.mix_prob <= 1.0:
+        parser.error("--mix-prob must be in [0, 1]")
+    if mixing and args.parallel == "pipe":
+        parser.error("--mixup-alpha / --cutmix-alpha with --parallel pipe is not supported "
+                     "(images enter at stage 0, labels are used at the last stage)")
     world = args.world_size or int(os.environ.get("WORLD_SIZE", "1"))
     if args.clip_grad_norm and args.parallel == "pipe" and world > 1:
         parser.error("--clip-grad-norm with --parallel pipe at world size > 1 is not supported "
@@ -105,6 +119,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help=f"--optimizer lars: trust ratio = ETA |w| / (|g| + wd |w| + eps) (default {TRUST_COEFFICIENT})")
     p.add_argument("--clip-grad-norm", default=0.0, type=float, metavar="X",
                    help="--optimizer adamw: clip the global gradient norm to X (0 = off)")
+    p.add_argument("--label-smoothing", default=0.0, type=float, metavar="E",
+                   help="training loss: weight E spread uniformly over the classes, in [0, 1) "
+                        "(validation loss stays plain)")
+    p.add_argument("--mixup-alpha", default=0.0, type=float, metavar="A",
+                   help="mixup with lam ~ Beta(A, A) on the training batches (0 = off; not with --parallel pipe); "
+                        "acc1_train stays top-1 against each sample's own (first) label")
+    p.add_argument("--cutmix-alpha", default=0.0, type=float, metavar="A",
+                   help="CutMix with lam ~ Beta(A, A) (0 = off); with --mixup-alpha each mixed batch picks one "
+                        "of the two with equal odds; acc1_train as for --mixup-alpha")
+    p.add_argument("--mix-prob", default=None, type=float, metavar="P",
+                   help="probability that a training batch is mixed (default 1.0; needs an alpha)")
     p.add_argument("-r", "--resume", action="store_true")
     p.add_argument("--arch", default="mobilenetv2")
     p.add_argument("--parallel", default="ddp", choices=["ddp", "dp", "pipe", "none"])
@@ -230,10 +255,17 @@ def run_data_parallel(args, env) -> None:
             x = x.contiguous(memory_format=torch.channels_last)
         return x, y.to(dev, non_blocking=True)
 
+    mixer = None
+    if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
+        from ..ops.mix import BatchMixer
+        mixer = BatchMixer(args.mixup_alpha, args.cutmix_alpha, prob=args.mix_prob, seed=args.seed,
+                           rank=env.rank if args.parallel == "ddp" else 0)
     timer = StepTimer(dev)
     for epoch in range(start_epoch, args.epochs):
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if mixer is not None:
+            mixer.set_epoch(epoch)
         net.train()
         lm, am = AverageMeter(), AverageMeter()
         it = iter(train_loader)
@@ -245,8 +277,11 @@ def run_data_parallel(args, env) -> None:
                     break
                 x, y = to_dev(*batch)
             with timer.region("step"), trace_range("train.step"):
+                y_b, lam = None, 1.0
+                if mixer is not None:
+                    x, y, y_b, lam = mixer(x, y)
                 out = net(x)
-                loss = cross_entropy(out, y)
+                loss = cross_entropy(out, y, label_smoothing=args.label_smoothing, target_b=y_b, lam=lam)
                 loss.backward()
                 opt.step()
                 opt.zero_grad()
@@ -328,6 +363,7 @@ def run_pipeline(args, env) -> None:
     pipe = Pipeline(model.as_sequential(), comm, (c, h, w), micro_batches=args.micro_batches,
                     schedule=args.schedule, dtype=parse_dtype(args.dtype),
                     channels_last=args.channels_last, partition=args.partition,
+                    label_smoothing=args.label_smoothing,
                     # one GPU only (see train/step.py): multi-rank GPU pipelines run eagerly
                     graphs=env.device.type == "cuda" and not args.no_pipe_graphs and comm.size == 1)
     opt = _optimizer(args, pipe.module.parameters(), flat=False)

@@ -45,6 +45,7 @@ class StepConfig:
     eps: float = 1e-8               # optimizer == "adamw" / "lars"
     clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
     trust_coefficient: float = 1e-3  # optimizer == "lars"
+    label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -143,7 +144,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = wrapped(x)
-            loss = cross_entropy(out, y)
+            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -158,7 +159,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = wrapped(x)
-            loss = cross_entropy(out, y)
+            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -169,7 +170,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = model(x)
-            loss = cross_entropy(out, y)
+            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -204,6 +205,7 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
                     schedule=cfg.schedule, device=device, dtype=cfg.dtype,
                     channels_last=cfg.channels_last, partition=cfg.partition,
                     static_batch=cfg.batch_size,  # every rank knows it: no per-step size message
+                    label_smoothing=cfg.label_smoothing,
                     # captured stage slots on one GPU only: the multi-stage slot
                     # schedule is verified on the CPU stand-ins (tests/test_pipeline.py)
                     # but never with RCCL between captured stages (a 1-GPU box cannot
