@@ -177,7 +177,7 @@ void set_wgrad3x3_waves(int64_t nw);
 // ---- data/batch_mix.hip ----
 at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, const std::vector<int64_t>& box);
 
-// ---- gemm/gemm_xl.hip (NT) ----
+// ---- gemm/gemm_xl.hip (NT: host side; kernels in gemm_xl_nt8.hip, gemm_xl_w4.hip, gemm_xl_x2.hip) ----
 at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& mode,
                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& aux,
                    const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& out);

@@ -56,7 +56,7 @@ __device__ __attribute__((aligned(32))) float g_nt_zero[16] = {};
 enum Epi { EPI_STORE = 0, EPI_MOMENTS = 1, EPI_AFFINE = 2, EPI_BNBWD = 3,
            // EPI_BNBWD with the mask taken from the BN output y, fixed at compile
            // time (with / without the x moments); plain EPI_BNBWD = mask from x
-           // (gemm_xl.hip finding 55: the runtime operand flags cost the epilogue)
+           // (gemm/xl_nt.h XlEpi, finding 55: the runtime operand flags cost the epilogue)
            EPI_BNBWD_Y = 4, EPI_BNBWD_YO = 5 };
 __host__ __device__ constexpr bool nt_bnbwd(int e) { return e == EPI_BNBWD || e == EPI_BNBWD_Y || e == EPI_BNBWD_YO; }
 
@@ -425,10 +425,10 @@ void gemm_nt_kernel(const NtArgs p) {
   // Phase 1 issues every global operand load of the tile's row passes
   // (residual / BN input / BN output), phase 2 computes and stores: loads that
   // sit behind possibly-aliasing stores would keep ~2 per lane in flight
-  // (tools/epi_bench.py; same structure as gemm_xl.hip's conv epilogues).
+  // (tools/epi_bench.py; same structure as the conv epilogues of gemm/xl_nt.h's xl_epilogue).
   constexpr int NP = BM / RPP;
   constexpr bool kLR = nt_bnbwd(EPI) || EPI == EPI_AFFINE;
-  // branch-free operand loads (dummy row 0 of C when an operand is absent; see gemm_xl.hip)
+  // branch-free operand loads (dummy row 0 of C when an operand is absent; see xl_epilogue in gemm/xl_nt.h)
   const bf16* rbase = R ? R : C;
   const int64_t rld = R ? ldr : 0;
   const bf16* xbase = bnx ? bnx : C;

@@ -1,15 +1,26 @@
-// What the large-tile NT kernels (gemm_xl.hip) and TN kernels (gemm_tn_xl.hip)
-// share: the K tile and block size, the LDS-DMA copy, counted waits and the
-// raw barrier, the implicit-GEMM conv view, the zero row of padding taps, the
-// tied-accumulator MFMA of the 4-wave kernels and the operand check.
-// Everything is in an unnamed namespace: each of the two sources gets its own
-// copy (g_zero_row included).
+// What the large-tile NT kernels (gemm_xl_nt8.hip, gemm_xl_w4.hip,
+// gemm_xl_x2.hip and their host file gemm_xl.hip, through xl_nt.h) and TN
+// kernels (gemm_tn_xl.hip) share: the K tile and block size, the LDS-DMA copy,
+// counted waits and the raw barrier, the implicit-GEMM conv view, the zero row
+// of padding taps, the tied-accumulator MFMA of the 4-wave kernels and the
+// operand check.  Everything but XlConv (a member of structs that cross
+// translation units) is in an unnamed namespace: each source gets its own copy
+// (g_zero_row included).
 #pragma once
 
 #include <torch/extension.h>
 #include "../common.h"
 
 namespace dmp {
+
+// Implicit-GEMM convolution view of an operand (the 256 x 256 kernels only):
+// GEMM row m is output pixel (n, oh, ow) of an NHWC input [N, Hi, Wi, cin]; K
+// tile kt is channels c0..c0+63 of tap (tr, tc), K = taps * cin.  cin == 0:
+// plain GEMM.
+struct XlConv {
+  int cin = 0, hi = 0, wi = 0, ho = 0, wo = 0, stride = 1, pad = 0, kw = 1;
+};
+
 namespace {
 
 using bf16 = __bf16;
@@ -32,14 +43,6 @@ __device__ __forceinline__ void barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-
-// Implicit-GEMM convolution view of an operand (the 256 x 256 kernels only):
-// GEMM row m is output pixel (n, oh, ow) of an NHWC input [N, Hi, Wi, cin]; K
-// tile kt is channels c0..c0+63 of tap (tr, tc), K = taps * cin.  cin == 0:
-// plain GEMM.
-struct XlConv {
-  int cin = 0, hi = 0, wi = 0, ho = 0, wo = 0, stride = 1, pad = 0, kw = 1;
-};
 
 // 16-B reads of padding taps land here (LDS-DMA cannot write zeros itself).
 __device__ __attribute__((aligned(16))) bf16 g_zero_row[128] = {};

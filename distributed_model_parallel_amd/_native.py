@@ -82,8 +82,8 @@ def require(what: str = "this operation") -> ModuleType:
 FEATURES = {
     "igemm": "every native 3x3 conv (ops/conv_igemm.py) -> MIOpen",
     "halo3": "halo-tiled 3x3 convs of layers 1-2 (conv3x3_halo.hip, conv3x3_c128.hip)",
-    "xl_conv3": "256x256 ping-pong implicit GEMM for layer-3/4 3x3 convs (gemm_xl.hip conv_xl)",
-    "xl_conv": "256x256 ping-pong GEMM for wide 1x1 convs (gemm_xl.hip)",
+    "xl_conv3": "256x256 implicit GEMM for layer-3/4 3x3 convs (gemm_xl.hip conv_xl; kernels gemm_xl_w4.hip, gemm_xl_nt8.hip)",
+    "xl_conv": "256x256 GEMM for wide 1x1 convs (gemm_xl.hip gemm_xl_conv; kernels gemm_xl_w4.hip, gemm_xl_nt8.hip, gemm_xl_x2.hip)",
     "tn_xl": "ping-pong TN weight gradients of wide 1x1 convs and of the ViT linears",
     "xl_linear": "ViT MLP / attention projection on the fused-epilogue ping-pong GEMM -> hipBLASLt + GELU / add passes",
     "compact_shortcut": "stride-2 shortcut gradient kept compact (no zero-filled tensor)",

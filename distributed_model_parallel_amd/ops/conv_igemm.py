@@ -58,7 +58,7 @@ def _capturing() -> bool:
 
 # Weight gradients of 3x3 convs the halo kernel does not cover with Cin % 256
 # == 0 (layer 4's stride-2 first block; any layer-3/4 shape at small maps) on
-# the TN tap-gather kernel (gemm_xl.hip conv_wgrad_xl) instead of MIOpen's
+# the TN tap-gather kernel (gemm_tn_xl.hip conv_wgrad_xl) instead of MIOpen's
 # igemm_wrw, at every size since round 6: its 4-wave form (gemm_tn_w4 with
 # the incremental pixel walk) takes the ResNet-50 layer-3/4 3x3 weight
 # gradients at batch 2048 in 0.49-0.52 ms against MIOpen's 0.66-0.78

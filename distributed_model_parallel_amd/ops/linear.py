@@ -12,7 +12,7 @@
 
 * ``mlp_residual`` / ``linear_residual``: the ViT block's MLP and attention
   output projection with the residual add, on our 256x256 ping-pong MFMA GEMM
-  (``csrc/gemm/gemm_xl.hip``, PIPE 7) and its fused epilogues: fc1 writes the
+  (``csrc/gemm/gemm_xl.hip``; kernels in ``gemm_xl_w4.hip`` / ``gemm_xl_nt8.hip``) and its fused epilogues: fc1 writes the
   pre-activation and GELU(h) in one pass (no GELU kernel), fc2 / proj add bias
   and residual in the store (no add kernel), and fc2's data gradient applies
   gelu'(h) in its epilogue (no GELU-backward pass).  On by default since the
@@ -87,7 +87,7 @@ _TN_MIN_ROWS = 16384
 
 
 def _gemm_operand_ok(t: torch.Tensor) -> bool:
-    """What csrc/gemm/gemm_xl.hip check_bf16_2d demands of a GEMM operand:
+    """What csrc/gemm/xl_common.h check_bf16_2d demands of a GEMM operand:
     2-D bf16, unit column stride, 16-B aligned rows and base (a column-sliced
     or offset view fails here and takes the library path instead of raising
     in the kernel's TORCH_CHECK)."""

@@ -86,3 +86,81 @@ def test_xl_conv_pingpong_schedule(mode, pipe):
         C.set_gemm_xl_bn(0)
     torch.testing.assert_close(got.float(), ref.float(), atol=0.02, rtol=1e-2)
     torch.testing.assert_close(gs, rs, atol=1e-2 * M ** 0.5, rtol=1e-3)
+
+
+# ---- every conv epilogue under every main-loop / tile-width / x2 setting ----
+# M = 300: one full 256-row tile and a ragged one.  N = 384 = 128 + 256: the
+# two-blocks-per-CU route at x2 mode 1, a ragged last 256-wide tile otherwise.
+# K = 192: three K tiles (prologue, steady state, drain of every main loop).
+_RM, _RN, _RK = 300, 384, 192
+_ROUTE_CASES = ["moments", "add", "affine", "affine-res-relu", "bnbwd-x", "bnbwd-xy", "bnbwd-y"]
+
+
+@pytest.fixture(scope="module")
+def route_ref():
+    """Operands of every case and this file's reference for it (gemm_nt /
+    gemm_nt_bnbwd, which the xl knobs do not reach), computed once."""
+    C = _native.require("gemm_xl_conv")
+    M, N, K = _RM, _RN, _RK
+    torch.manual_seed(21)
+    a = torch.randn(M, K, device=DEV).bfloat16()
+    b = (torch.randn(N, K, device=DEV) * 0.1).bfloat16()
+    r = torch.randn(M, N, device=DEV).bfloat16()
+    x = torch.randn(M, N, device=DEV).bfloat16()
+    mean = x.float().mean(0)
+    inv = torch.rand(N, device=DEV) + 0.5
+    bw = torch.rand(N, device=DEV) + 0.5
+    bb = torch.randn(N, device=DEV) * 0.5
+    y = torch.relu(x.float() * inv * bw + bb - mean * inv * bw).bfloat16()
+    sc = torch.rand(N, device=DEV) + 0.5
+    sh = torch.randn(N, device=DEV)
+    kw = {
+        "moments": {},
+        "add": dict(residual=r),
+        "affine": dict(scale=sc, shift=sh),
+        "affine-res-relu": dict(scale=sc, shift=sh, residual=r, relu=True),
+        "bnbwd-x": dict(residual=r, bn_x=x, mean=mean, invstd=inv, weight=bw, bias=bb),
+        "bnbwd-xy": dict(residual=r, bn_x=x, bn_y=y, mean=mean),
+        "bnbwd-y": dict(residual=r, bn_y=y),
+    }
+    ref = {
+        "moments": C.gemm_nt(a, b)[0],
+        "add": C.gemm_nt(a, b, mode="add", residual=r)[0],
+        "affine": C.gemm_nt(a, b, mode="affine", epi_scale=sc, epi_shift=sh)[0],
+        "affine-res-relu": C.gemm_nt(a, b, mode="affine", epi_scale=sc, epi_shift=sh, residual=r, relu=True)[0],
+        "bnbwd-x": C.gemm_nt_bnbwd(a, b, r, x, None, mean, inv, bw, bb)[0],
+        "bnbwd-xy": C.gemm_nt_bnbwd(a, b, r, x, y, mean, None, None, None)[0],
+        "bnbwd-y": C.gemm_nt_bnbwd(a, b, r, None, y, None, None, None, None)[0],
+    }
+    return a, b, kw, {k: v.float() for k, v in ref.items()}, x.double() - mean.double()
+
+
+@pytest.mark.parametrize("x2", [0, 1])
+@pytest.mark.parametrize("setting", [(0, -1), (128, 1), (256, 1), (128, 0), (256, 0), (256, 10), (256, 11)],
+                         ids=["auto", "bn128", "bn256", "bn128-pipe0", "bn256-pipe0", "bn256-pingpong", "bn256-w4"])
+@pytest.mark.parametrize("case", _ROUTE_CASES)
+def test_xl_conv_every_route(route_ref, case, setting, x2):
+    """Each gemm_xl_conv mode and bnbwd operand form lands on the right
+    kernel instantiation under every (bn, pipe) setting of test_gpu_gemm_xl's
+    `bn` fixture and both x2 modes.  This file's references are the gemm_nt
+    kernels (same math, same rounding points) and fp64 sums of what was
+    stored, at this file's tolerances; the affine cases, which it did not
+    cover, take gemm_nt's affine epilogue at the same tolerance as "add"."""
+    C = _native.require("gemm_xl_conv")
+    a, b, kw, ref, xc = route_ref
+    N = _RN
+    old_pipe, old_x2 = C.get_gemm_xl_pipe(), C.get_gemm_xl_x2()
+    C.set_gemm_xl_bn(*setting)
+    C.set_gemm_xl_x2(x2)
+    try:
+        c, sums = C.gemm_xl_conv(a, b, case.split("-")[0], **kw[case])
+    finally:
+        C.set_gemm_xl_bn(0, old_pipe)
+        C.set_gemm_xl_x2(old_x2)
+    torch.testing.assert_close(c.float(), ref[case], atol=2e-2, rtol=1e-2)
+    if case == "moments" or case.startswith("bnbwd"):
+        cd = c.double()
+        second = cd * cd if case == "moments" else cd * xc if "x" in case.split("-")[1] else torch.zeros_like(cd)
+        torch.testing.assert_close(sums[:N], cd.sum(0), atol=1e-2, rtol=1e-4)
+        torch.testing.assert_close(sums[N:2 * N], second.sum(0), atol=1e-2, rtol=1e-4)
+        assert sums[2 * N].item() == _RM

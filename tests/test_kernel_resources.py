@@ -1,4 +1,4 @@
-"""Build-time guard for the 4-wave GEMMs (gemm_xl.hip PIPE 11 and
+"""Build-time guard for the 4-wave GEMMs (gemm_xl_w4.hip, PIPE 11, and
 gemm_tn_xl.hip's gemm_tn_w4_kernel): their MFMAs are
 inline asm with the accumulators pinned to AGPRs, so the compiler does not
 know they are still being written for ~18 cycles after each issue.  Any
@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
                     reason="needs hipcc and c++filt")
 def test_w4_gemm_kernels_never_spill():
     from tools.kernel_resources import resources
-    ks = [k for src in ("gemm_xl.hip", "gemm_tn_xl.hip")  # the NT and the TN 4-wave kernels
+    ks = [k for src in ("gemm_xl_w4.hip", "gemm_tn_xl.hip")  # the NT and the TN 4-wave kernels
           for k in resources(os.path.join(ROOT, "csrc", "gemm", src))
           if k["name"].startswith(("gemm_xl_w4_kernel", "gemm_tn_w4_kernel"))]
     assert len(ks) >= 20, [k["name"] for k in ks]

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bf16 GEMM backends side by side on one process (HIP events, random operands):
-our 4-wave NT kernel (csrc/conv/gemm_bf16.hip ``gemm_nt``), the 8-wave
-256-row glds-ring kernel (csrc/gemm/gemm_xl.hip ``gemm_xl``) and hipBLASLt
+our 4-wave NT kernel (csrc/conv/gemm_bf16.hip ``gemm_nt``), the 256-row
+large-tile kernels (``gemm_xl`` of csrc/gemm/gemm_xl.hip: gemm_xl_w4.hip by
+default, gemm_xl_nt8.hip under the other pipes) and hipBLASLt
 (``torch.mm`` with the tuned solutions in effect).  Shapes: square sizes, the
 ViT-B/16 linears at batch 256 (197 tokens) and the ResNet-50 implicit-GEMM
 shapes at batch 1024 taken as plain GEMMs.  Markdown table on stdout.

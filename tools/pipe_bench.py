@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""A/B of the 256 x 256 main loops (csrc/gemm/gemm_xl.hip): PIPE 10 (8-wave
-ping-pong, both B halves held in registers, copies issued 4 phases ahead) vs
-PIPE 11 (4 waves, 128 x 128 per wave in AGPRs, full-line LDS-DMA), for
+"""A/B of the 256 x 256 main loops (selected in csrc/gemm/gemm_xl.hip): PIPE 10
+(gemm_xl_nt8.hip: 8-wave ping-pong, both B halves held in registers, copies
+issued 4 phases ahead) vs PIPE 11 (gemm_xl_w4.hip: 4 waves, 128 x 128 per
+wave in AGPRs, full-line LDS-DMA), for
 the NT kernel (gemm_xl store / conv epilogues / 3x3 implicit GEMM) and the TN
 weight-gradient kernel (gemm_tn_xl), on the ViT-B/16 and ResNet-50 shapes
 that carry the step time, plus hipBLASLt (torch.matmul) on the plain shapes.

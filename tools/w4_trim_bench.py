@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the 4-wave GEMM's tile height (csrc/gemm/gemm_xl.hip
+"""A/B of the 4-wave GEMM's tile height (csrc/gemm/gemm_xl_w4.hip
 gemm_xl_w4_kernel MB = 8 / 7: 256- vs 224-row tiles) on the grids whose last
 1-block/CU round is partial, plus hipBLASLt (torch.mm) on the plain ones.
 Interleaved rounds in one process, random operands; median ms and TF/s.

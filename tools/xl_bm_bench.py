@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Trimmed ping-pong tiles (gemm_xl.hip pick_bm) against 256-row tiles, on
+"""Trimmed ping-pong tiles (gemm_xl.hip pick_bm; kernels gemm_xl_nt8.hip / gemm_xl_w4.hip) against 256-row tiles, on
 the MFMA-bound shapes whose last round of 256-row tiles is partly empty:
 ResNet-50's layer-3/4 3x3 convolutions (forward with BN moments, data
 gradient with the BN backward) at batch 2048, and ViT-B/16's N = 768 GEMMs

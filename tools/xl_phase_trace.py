@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Where a 256 x 256 GEMM tile's time goes (gemm_xl.hip, the 4-wave PIPE 11
-kernel or the 8-wave ping-pong PIPE 10 one, whichever the dispatch picks;
+"""Where a 256 x 256 GEMM tile's time goes (the 4-wave PIPE 11 kernel of
+gemm_xl_w4.hip or the 8-wave ping-pong PIPE 10 one of gemm_xl_nt8.hip,
+whichever xl_launch in gemm_xl.hip picks;
 set_gemm_xl_trace): per block, thread 0 records the realtime clock (10 ns) at
 entry, when the first K tile's operands have landed, after the main loop and
 after the epilogue, plus the HW_ID / XCC_ID registers that name its CU.  This
