@@ -21,6 +21,8 @@ namespace dmp {
 bool attention_supported(int64_t S, int64_t head_dim);
 void set_attention_variant(int fwd, int bwd);
 std::vector<int64_t> get_attention_variant();
+void set_attention_long_from(int64_t n);
+int64_t get_attention_long_from();
 std::vector<at::Tensor> attention_forward(const at::Tensor& qkv, int64_t B, int64_t S, int64_t H, double scale);
 at::Tensor attention_backward(const at::Tensor& dout, const at::Tensor& qkv, const at::Tensor& o,
                               const at::Tensor& lse, int64_t B, int64_t S, int64_t H, double scale);

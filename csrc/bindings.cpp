@@ -237,7 +237,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("get_attention_variant", &dmp::get_attention_variant);
   m.def("set_attention_variant", &dmp::set_attention_variant, py::arg("fwd"), py::arg("bwd") = 1,
         "attention kernels: fwd 0 = one workgroup per (batch, head), 1 = persistent with next-head prefetch, "
-        "2 = 8-wave per head; bwd 0 = per head, 1 = persistent with prefetch");
+        "2 = 8-wave per head; bwd 0 = per head, 1 = persistent with prefetch.  Selects among the S <= 256 "
+        "kernels only: the streamed long-sequence kernels (set_attention_long_from) have one variant each");
+  m.def("get_attention_long_from", &dmp::get_attention_long_from);
+  m.def("set_attention_long_from", &dmp::set_attention_long_from, py::arg("n"),
+        "sequences of n tokens or more run the streamed long-sequence attention kernels (default 257: "
+        "everything the whole-sequence-in-LDS kernels cannot hold; 1 = always, for A/B runs and tests)");
   m.def("attention_forward", &dmp::attention_forward, py::arg("qkv"), py::arg("B"), py::arg("S"),
         py::arg("H"), py::arg("scale"),
         py::call_guard<py::gil_scoped_release>());

@@ -126,6 +126,27 @@ class VisionTransformer(nn.Module):
         return self.head(self.ln(x)[:, 0])
 
 
+def resize_pos_embedding(pos: torch.Tensor, n_tokens_new: int) -> torch.Tensor:
+    """Position embedding [1, 1 + g*g, D] for another square patch grid
+    (fine-tuning at a different resolution): the class-token row is kept as it
+    is, the grid rows are interpolated bicubically in fp32 on their g x g
+    layout and cast back.  Returns `pos` itself when the size already matches."""
+    n_old = pos.shape[1]
+    if n_old == n_tokens_new:
+        return pos
+    g_old, g_new = math.isqrt(n_old - 1), math.isqrt(n_tokens_new - 1)
+    if pos.dim() != 3 or pos.shape[0] != 1 or g_old * g_old != n_old - 1 or g_new * g_new != n_tokens_new - 1 \
+            or g_old < 1 or g_new < 1:
+        raise ValueError(f"resize_pos_embedding: need [1, 1 + g*g, D] embeddings, got {tuple(pos.shape)} "
+                         f"-> {n_tokens_new} tokens")
+    cls, grid = pos[:, :1], pos[:, 1:]
+    d = pos.shape[2]
+    grid = grid.float().reshape(1, g_old, g_old, d).permute(0, 3, 1, 2)
+    grid = F.interpolate(grid, size=(g_new, g_new), mode="bicubic", align_corners=False)
+    grid = grid.permute(0, 2, 3, 1).reshape(1, g_new * g_new, d).to(pos.dtype)
+    return torch.cat([cls, grid], 1)
+
+
 def vit_b_16(num_classes: int = 1000, image_size: int = 224, **kw) -> VisionTransformer:
     return VisionTransformer(image_size, 16, 12, 12, 768, 3072, num_classes, **kw)
 

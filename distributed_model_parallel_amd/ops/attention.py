@@ -1,9 +1,12 @@
 """Multi-head self-attention on the packed qkv projection output, on our HIP
-kernels (``csrc/attn/attention.hip``): forward and backward read qkv
-[B*S, 3*H*64] and write o [B*S, H*64] / dqkv [B*S, 3*H*64] directly, so the
-head split/permute copies, the output transpose and the dq/dk/dv
-concatenation of the generic SDPA path disappear.  ViT-sized sequences
-(S <= 256) with head dim 64; anything else (CPU, dropout, other shapes) runs
+kernels: forward and backward read qkv [B*S, 3*H*64] and write o [B*S, H*64] /
+dqkv [B*S, 3*H*64] directly, so the head split/permute copies, the output
+transpose and the dq/dk/dv concatenation of the generic SDPA path disappear.
+Head dim 64; S <= 256 (ViT-B/16 at 224 px) runs ``csrc/attn/attention.hip``
+(whole sequence in LDS), 257 <= S <= 4096 (384 px: 577 tokens) the streamed
+kernels of ``csrc/attn/attention_long.hip`` behind the same entry points
+(``_C.set_attention_long_from`` moves the threshold down for A/B runs);
+anything else (CPU, dropout, other shapes) runs
 ``F.scaled_dot_product_attention``."""
 from __future__ import annotations
 

@@ -32,6 +32,7 @@ import torch.nn.functional as F
 
 
 TRUST_COEFFICIENT = 1e-3  # --trust-coefficient when the flag is absent
+_VIT_PATCH = {"vit_b_16": 16, "vit_tiny": 8}  # --image-size must be a multiple of it
 
 
 def _betas(text: str):
@@ -68,6 +69,22 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
     if mixing and args.parallel == "pipe":
         parser.error("--mixup-alpha / --cutmix-alpha with --parallel pipe is not supported "
                      "(images enter at stage 0, labels are used at the last stage)")
+    if args.image_size is not None:
+        if not args.arch.startswith("vit"):
+            parser.error(f"--image-size is for ViT archs only (vit_b_16, vit_tiny), not --arch {args.arch}")
+        patch = _VIT_PATCH.get(args.arch, 16)
+        if args.image_size < patch or args.image_size % patch:
+            parser.error(f"--image-size must be a positive multiple of the patch size {patch} of {args.arch}")
+        if args.parallel == "pipe":
+            parser.error("--image-size with --parallel pipe is not supported")
+    if args.init_from:
+        if not os.path.exists(args.init_from):
+            parser.error(f"--init-from: no such file {args.init_from}")
+        if args.resume and os.path.exists(args.checkpoint):
+            parser.error(f"--init-from and --resume from an existing checkpoint ({args.checkpoint}) "
+                         "are mutually exclusive")
+        if args.parallel == "pipe":
+            parser.error("--init-from with --parallel pipe is not supported")
     world = args.world_size or int(os.environ.get("WORLD_SIZE", "1"))
     if args.clip_grad_norm and args.parallel == "pipe" and world > 1:
         parser.error("--clip-grad-norm with --parallel pipe at world size > 1 is not supported "
@@ -131,6 +148,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mix-prob", default=None, type=float, metavar="P",
                    help="probability that a training batch is mixed (default 1.0; needs an alpha)")
     p.add_argument("-r", "--resume", action="store_true")
+    p.add_argument("--init-from", default="", metavar="CKPT",
+                   help="initialise the model from CKPT's weights only (fine-tuning: no optimizer / scheduler / "
+                        "RNG state; a ViT position embedding of another resolution is resized bicubically); "
+                        "not together with --resume from an existing checkpoint")
+    p.add_argument("--image-size", default=None, type=int, metavar="N",
+                   help="ViT archs only: train at N x N pixels (model, ImageNet transforms and synthetic data)")
     p.add_argument("--arch", default="mobilenetv2")
     p.add_argument("--parallel", default="ddp", choices=["ddp", "dp", "pipe", "none"])
     p.add_argument("--bucket-cap-mb", default=25.0, type=float)
@@ -170,9 +193,16 @@ def _datasets(args):
     from ..data import DatasetCollection, transforms as T
     cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
     if args.synthetic or not args.data:
+        if args.image_size is not None:  # the stock synthetic sets, at the ViT's own resolution
+            from ..data import SyntheticImages
+            shape, nc = (3, args.image_size, args.image_size), _num_classes(args)
+            n_train, n_val = (5000, 1000) if _synthetic_kind(args) == "SyntheticCIFAR" else (1281, 500)
+            return SyntheticImages(n_train, shape, nc), SyntheticImages(n_val, shape, nc, seed=1)
         return DatasetCollection(_synthetic_kind(args), "").init()
     if cifar:
         tr, va = T.cifar_train_transform(), T.cifar_test_transform()
+    elif args.image_size is not None:
+        tr, va = T.imagenet_train_transform(args.image_size), T.imagenet_val_transform(args.image_size)
     else:
         tr, va = T.imagenet_train_transform(), T.imagenet_val_transform()
     return DatasetCollection(args.dataset_type, args.data, tr, va).init()
@@ -217,7 +247,11 @@ def run_data_parallel(args, env) -> None:
 
     dev = env.device
     dtype = parse_dtype(args.dtype)
-    model = build_model(args.arch, num_classes=_num_classes(args))
+    size_kw = {} if args.image_size is None else {"image_size": args.image_size}
+    model = build_model(args.arch, num_classes=_num_classes(args), **size_kw)
+    if args.init_from:
+        from ..utils.checkpoint import load_weights
+        load_weights(args.init_from, model)  # before the cast and the optimizer: masters start from these
     if args.checkpoint_segments > 1:
         from ..utils.checkpointing import enable_activation_checkpointing
         enable_activation_checkpointing(model, args.checkpoint_segments)

@@ -141,6 +141,31 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
     return {"epoch": state.get("epoch", 0), "acc": state.get("acc", 0.0), "extra": state.get("extra", {})}
 
 
+def load_weights(path: str, model: nn.Module, map_location=None) -> Dict[str, Any]:
+    """Initialise `model` from the weights of a checkpoint (fine-tuning): the
+    ``net`` entry only -- no optimizer, scheduler or RNG state, and the
+    checkpoint's epoch / accuracy do not carry over.  A ViT ``pos_embedding``
+    of another token count is resized onto the model's patch grid
+    (``models.vit.resize_pos_embedding``); any other mismatch raises.  Call it
+    before the optimizer is built, so fp32 master weights start from the
+    loaded values."""
+    state = _load_weights_only(path, map_location or "cpu")
+    sd = dict(_strip_prefix(state["net"] if isinstance(state, dict) and "net" in state else state))
+    target = unwrap(model)
+    own = target.state_dict()
+    resized = False
+    pe = "pos_embedding"
+    if pe in sd and pe in own and sd[pe].shape != own[pe].shape:
+        from ..models.vit import resize_pos_embedding
+        sd[pe] = resize_pos_embedding(sd[pe], own[pe].shape[1])
+        resized = True
+    target.load_state_dict(sd, strict=True)  # raises on any remaining shape or key mismatch
+    ddp = model if hasattr(model, "reducer") else None
+    if ddp is not None and ddp.world_size > 1:
+        ddp._sync_module_states()
+    return {"pos_embedding_resized": resized}
+
+
 def _load_weights_only(path: str, map_location):
     """``torch.load(weights_only=True)``: tensors / containers / numbers only,
     nothing in the file is executed.  Files written before the RNG state became

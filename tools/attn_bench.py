@@ -34,7 +34,9 @@ def sdpa_path(qkv, heads):
 
 
 def main():
-    B, S, H = int(os.environ.get("B", 128)), 197, 12
+    # B, S, H from the environment; S > 256 (ViT-B/16 at 384 px: S=577) times the streamed
+    # long-sequence kernels, which have no variants
+    B, S, H = int(os.environ.get("B", 128)), int(os.environ.get("S", 197)), int(os.environ.get("H", 12))
     # VARIANT="f,b" ITERS=n: only that variant, n forward + backward passes (profiling)
     only = os.environ.get("VARIANT")
     qkv = torch.randn(B, S, 3 * H * 64, device="cuda", dtype=torch.bfloat16, requires_grad=True)
@@ -54,12 +56,26 @@ def main():
         torch.cuda.synchronize()
         print("done", only)
         return
-    for name, fn in (("sdpa+copies", lambda: sdpa_path(qkv, H)), ("hip per-head", variant(0, 0)),
-                     ("hip persistent", variant(1, 1)), ("hip 8-wave fwd", variant(2, 1)),
-                     ("hip pers fwd + per-head bwd", variant(1, 0)), ("hip 2-tile fwd", variant(3, 0))):
+    def long_path(n):
+        def f():
+            C.set_attention_long_from(n)
+            return A.self_attention_packed(qkv, H)
+        return f
+    long_from = C.get_attention_long_from()
+    rows = [("sdpa+copies", lambda: sdpa_path(qkv, H))]
+    if S >= long_from:
+        rows.append(("hip long", long_path(long_from)))
+    else:
+        rows += [("hip per-head", variant(0, 0)), ("hip persistent", variant(1, 1)),
+                 ("hip 8-wave fwd", variant(2, 1)), ("hip pers fwd + per-head bwd", variant(1, 0)),
+                 ("hip 2-tile fwd", variant(3, 0)), ("hip long (forced)", long_path(1))]
+    print(f"B={B} S={S} H={H}", flush=True)
+    for name, fn in rows:
         tf = timeit(lambda: fn())
         o = fn()
+        # the backward dispatches on the threshold too: keep this row's setting while it is timed
         tb = timeit(lambda: torch.autograd.grad(o, qkv, go, retain_graph=True))
+        C.set_attention_long_from(long_from)
         fl = 4.0 * B * H * S * S * 64
         print(f"{name:12s} fwd {tf:.3f} ms ({fl / tf / 1e9:.0f} TF/s)  bwd {tb:.3f} ms ({2.5 * fl / tb / 1e9:.0f} TF/s)"
               f"  total {tf + tb:.3f} ms", flush=True)
