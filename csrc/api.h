@@ -166,6 +166,9 @@ at::Tensor pad_channels16(const at::Tensor& x, int64_t pad, int64_t extra_w);
 bool stem_halo_supported(int64_t hs, int64_t ws, int64_t ho, int64_t wo);
 std::vector<at::Tensor> stem_halo_fwd(const at::Tensor& s, const at::Tensor& wm, int64_t ho, bool moments);
 at::Tensor stem_halo_wgrad(const at::Tensor& dy, const at::Tensor& s, int64_t ho, at::ScalarType out_dtype);
+std::vector<at::Tensor> stem_halo_wgrad_pool(const at::Tensor& dy, const at::Tensor& idx, const at::Tensor& y,
+                                             const at::Tensor& s, const at::Tensor& scale, const at::Tensor& shift,
+                                             const at::Tensor& mean, int64_t ho, int64_t pad);
 at::Tensor stem_fold_finish(const at::Tensor& img, int64_t ho, int64_t wo, const at::Tensor& t_dz,
                             const at::Tensor& t_y, const at::Tensor& sums, const at::Tensor& cnt,
                             const at::Tensor& invstd, const c10::optional<at::Tensor>& weight, const at::Tensor& mean,

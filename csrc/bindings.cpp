@@ -133,6 +133,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_halo_wgrad", &dmp::stem_halo_wgrad, py::arg("dy"), py::arg("s"), py::arg("ho"), py::arg("out_dtype"),
         "ResNet stem weight gradient [64, 256]: halo-tiled, dW in VGPRs",
         py::call_guard<py::gil_scoped_release>());
+  m.def("stem_halo_wgrad_pool", &dmp::stem_halo_wgrad_pool, py::arg("dy"), py::arg("idx"), py::arg("y"), py::arg("s"),
+        py::arg("scale"), py::arg("shift"), py::arg("mean"), py::arg("ho"), py::arg("pad"),
+        "ResNet stem folded backward: (dz^T P, y^T P, BN-backward sums) with the pool / ReLU backward formed in LDS",
+        py::call_guard<py::gil_scoped_release>());
   m.def("wgrad3x3", &dmp::wgrad3x3, py::arg("dy"), py::arg("x"), py::arg("stride") = 1,
         "dW [C, C, 3, 3] (channels_last) of a 3x3/s1/p1 conv: persistent halo-tiled MFMA kernel",
         py::call_guard<py::gil_scoped_release>());

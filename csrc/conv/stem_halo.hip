@@ -32,6 +32,10 @@
 //   image needs no swizzle and every tap offset rides in the instruction's
 //   offset field.  Partials are summed in a fixed order (reproducible).
 //
+// stem_wgrad_pool: stem_wgrad for the folded backward (dz^T P and y^T P in one
+//   pass over y), the pool / ReLU backward dz formed per tile in LDS; see the
+//   kernel's own comment below.
+//
 // Reference: the torchvision ResNet stem the reference's image models use
 // (reference model_parallel.py:61 cudnn.benchmark).
 #include <torch/extension.h>
@@ -413,6 +417,320 @@ __global__ __launch_bounds__(256, 1) void stem_wgrad_kernel(const bf16* __restri
         pb[(16 * i + 4 * g + e) * kK + 64 * wave + 16 * j + (lane & 15)] = acc[i][j][e];
 }
 
+// ============================================================================
+// weight gradient with the pool / BN(+ReLU) backward formed in the kernel
+// ============================================================================
+// The folded stem backward (ops/fused.py _StemBNReLUMaxPoolFn) needs dz^T P and
+// y^T P, dz the pool-scattered, ReLU-masked gradient of the 3x3 / s2 pool over
+// y.  dz is a pure function of the pooled gradient, the argmax bytes and y, so
+// it is formed here per tile straight into LDS (never written to memory), with
+// bnpool_bwd_kernel's arithmetic (maxpool.hip): fp32 gather in that kernel's
+// window order, rounded to bf16, masked with fmaf(y, sc, sh) > 0.  The tile
+// partition, the k order and the MFMA sequence per accumulator are those of
+// stem_wgrad_kernel, so both results are bit-identical to its two calls; the B
+// fragments (s) are read once for both accumulator sets.
+//
+// Forming: one item = a 2 x 2 quad of y pixels x 8 channels (56 quads x 8 = 448
+// items per tile, threads 0..191 take two).  A quad is covered by the 2 x 2
+// pooled outputs (kb + rr, cb + cc), kb = tile row - (1 - PAD), cb = quad
+// column - (1 - PAD); their dy / argmax vectors are loaded one tile ahead.
+constexpr int P_DZ = 2 * W_BUF;               // the dz tile, behind the two (y, s) stages
+constexpr int P_SMEM = P_DZ + W_DY_BYTES;     // 126976
+constexpr int P_ITEMS = (kWo / 2) * (kCo / 8);  // 448
+constexpr int P_OUT = 2 * kCo * kK;           // partial row: t_dz then t_y
+
+template <int PAD>
+__global__ __launch_bounds__(256, 1) void stem_wgrad_pool_kernel(
+    const bf16* __restrict__ dy, const uint8_t* __restrict__ idx, const bf16* __restrict__ y,
+    const bf16* __restrict__ s, const float* __restrict__ sc, const float* __restrict__ sh,
+    const float* __restrict__ mean, float* __restrict__ part, float* __restrict__ mpart, double* zsums, int Hs,
+    int Ho, int Hp, int Wp, int tiles, int tiles_per_img, int64_t s_bytes) {
+  static_assert(PAD == 0 || PAD == 1, "3x3 / s2 pool, pad 0 or 1");
+  __shared__ __attribute__((aligned(1024))) char smem[P_SMEM];
+  zero_moments(zsums, 2 * kCo);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int t_begin = (int)((int64_t)tiles * blockIdx.x / gridDim.x);
+  const int t_end = (int)((int64_t)tiles * (blockIdx.x + 1) / gridDim.x);
+  const int64_t img_bytes = (int64_t)Hs * kWs * kPixB;
+
+  // y DMA: stem_wgrad_kernel's dy slot (rows of 128 B, chunk XOR key)
+  int y_off[W_DY_PPW];
+#pragma unroll
+  for (int i = 0; i < W_DY_PPW; ++i) {
+    const int piece = wave + 4 * i;
+    const int row = piece * 8 + (lane >> 3);
+    y_off[i] = row * kCo + (((lane & 7) ^ dy_key(row)) * 8);
+  }
+  auto issue = [&](int t, char* buf) {
+    const int n = t / tiles_per_img;
+    const int r0 = (t - n * tiles_per_img) * WR;
+    const bf16* yb = y + (((int64_t)n * Ho + r0) * kWo) * kCo;
+#pragma unroll
+    for (int i = 0; i < W_DY_PPW; ++i) glds16(yb + y_off[i], buf + (wave + 4 * i) * 1024);
+    const int64_t start = n * img_bytes + (int64_t)r0 * kWs * kPixB;
+    const int64_t avail = s_bytes - start;
+    slab_issue<W_S_PPW, 4>(reinterpret_cast<const char*>(s) + start, avail < W_SLAB ? avail : W_SLAB,
+                           buf + W_DY_BYTES, wave, lane);
+  };
+
+  // forming geometry: item = tid (+ 256): quad column qc, channel vector cvi
+  const int cvi = tid & 7, c0 = cvi * 8;
+  const bool two = wave < (P_ITEMS - 256) / 64;  // waves 0..2
+  int qcol[2], fofs[2];
+  bool cok[2][2];
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int qc = (tid + 256 * it) >> 3;
+    qcol[it] = qc;
+    // dy_key is the same for the four pixels 112 dr + 2 qc + dc of a quad
+    fofs[it] = (2 * qc) * 128 + ((cvi ^ dy_key(2 * qc)) << 4);
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) cok[it][cc] = (unsigned)(qc - (1 - PAD) + cc) < (unsigned)Wp;
+  }
+  float s8[8], t8[8], mu[8], msum[8], msq[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    s8[c] = sc[c0 + c]; t8[c] = sh[c0 + c]; mu[c] = mean[c0 + c];
+    msum[c] = 0.f; msq[c] = 0.f;
+  }
+  u32x4 pg[2][2][2];    // [item][rr][cc] pooled gradient (8 bf16)
+  uint64_t pw[2][2][2];  // argmax bytes
+  auto pool_load = [&](int t) {
+    const int n = t / tiles_per_img;
+    const int kb = (t - n * tiles_per_img) - (1 - PAD);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      if (it == 1 && !two) continue;
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const int ohc = min(max(kb + rr, 0), Hp - 1);
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          const int owc = min(max(qcol[it] - (1 - PAD) + cc, 0), Wp - 1);
+          const int64_t o = (((int64_t)n * Hp + ohc) * Wp + owc) * kCo + c0;
+          pw[it][rr][cc] = *reinterpret_cast<const uint64_t*>(idx + o);
+          pg[it][rr][cc] = *reinterpret_cast<const u32x4*>(dy + o);
+        }
+      }
+    }
+  };
+  // dz of tile t from y (stage `yb`) and the pooled vectors in registers
+  auto form = [&](int t, const char* yb) {
+    const int n = t / tiles_per_img;
+    const int kb = (t - n * tiles_per_img) - (1 - PAD);
+    const bool rok[2] = {(unsigned)kb < (unsigned)Hp, (unsigned)(kb + 1) < (unsigned)Hp};
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      if (it == 1 && !two) continue;
+      // argmax bytes as two words; a window outside the pooled map matches no tap
+      f32x8 gv[2][2];
+      uint32_t wv[2][2][2];
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          gv[rr][cc] = __builtin_convertvector(__builtin_bit_cast(bf16x8, pg[it][rr][cc]), f32x8);
+          const bool ok = rok[rr] && cok[it][cc];
+          wv[rr][cc][0] = ok ? (uint32_t)pw[it][rr][cc] : 0xffffffffu;
+          wv[rr][cc][1] = ok ? (uint32_t)(pw[it][rr][cc] >> 32) : 0xffffffffu;
+        }
+#pragma unroll
+      for (int dr = 0; dr < 2; ++dr)
+#pragma unroll
+        for (int dc = 0; dc < 2; ++dc) {
+          const int po = fofs[it] + (dr * kWo + dc) * 128;
+          const f32x8 xv = __builtin_convertvector(*reinterpret_cast<const bf16x8*>(yb + po), f32x8);
+          float acc[8];
+#pragma unroll
+          for (int c = 0; c < 8; ++c) acc[c] = 0.f;
+          // windows (oh_hi - tt, ow_hi - uu) in bnpool_bwd_kernel's order; tap row
+          // a = (dr + PAD) % 2 + 2 tt (valid below 3), pooled row index rr below
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt) {
+            const int a = (dr + PAD) % 2 + 2 * tt;
+            const int rr = (dr + PAD) / 2 + (1 - PAD) - tt;
+            if (a >= 3) continue;
+#pragma unroll
+            for (int uu = 0; uu < 2; ++uu) {
+              const int b = (dc + PAD) % 2 + 2 * uu;
+              const int cc = (dc + PAD) / 2 + (1 - PAD) - uu;
+              if (b >= 3) continue;
+              const uint32_t tap = (uint32_t)(a * 3 + b);
+#pragma unroll
+              for (int c = 0; c < 8; ++c)
+                if (((wv[rr][cc][c >> 2] >> (8 * (c & 3))) & 0xffu) == tap) acc[c] += gv[rr][cc][c];
+            }
+          }
+          f32x8 d8;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const float gq = (float)(__bf16)acc[c];  // the pool gradient as the unfused pass stores it
+            const float d = fmaf(xv[c], s8[c], t8[c]) > 0.f ? gq : 0.f;
+            d8[c] = d;
+            msum[c] += d;
+            msq[c] = fmaf(d, xv[c] - mu[c], msq[c]);
+          }
+          *reinterpret_cast<bf16x8*>(smem + P_DZ + po) = __builtin_convertvector(d8, bf16x8);
+        }
+    }
+  };
+
+  // tr-read geometry of stem_wgrad_kernel
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int pin = 16 * (g >> 1) + 4 * (g & 1) + q;
+  const int lofs = (p & 1) * 8 + (p >> 1) * 16;
+  int a_base[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a_base[i] = pin * 128 + (((2 * i) ^ dy_key(pin)) << 4) + lofs;
+  int sb[W_KS][2];
+#pragma unroll
+  for (int ks = 0; ks < W_KS; ++ks)
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int pp = 32 * ks + 8 * r + pin;
+      const int oy = pp / kWo, ox = pp - oy * kWo;
+      // + this wave's tap row kh = wave; the tap column rides in the offset field
+      sb[ks][r] = ((oy + wave) * kWs + ox) * kPixB + p * 8 + W_DY_BYTES;
+    }
+
+  // wave w: taps 4 w .. 4 w + 3 x all 64 co, for dz (accz) and for y (accy)
+  f32x4 accz[4][4], accy[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) accz[i][j] = accy[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto mma_tile = [&](int cur) {
+    int sbc[W_KS][2], ayc[4], azc[4];
+#pragma unroll
+    for (int ks = 0; ks < W_KS; ++ks) {
+      asm volatile("" : "+v"(sb[ks][0]), "+v"(sb[ks][1]));
+      sbc[ks][0] = sb[ks][0] + cur * W_BUF;
+      sbc[ks][1] = sb[ks][1] + cur * W_BUF;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      ayc[i] = a_base[i] + cur * W_BUF;
+      azc[i] = a_base[i] + P_DZ;
+    }
+    auto rd = [&](int addr) -> v4i16 {
+      return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(smem + addr));
+    };
+    auto rd2 = [&](int lo_addr, int hi_addr) -> bf16x8 {
+      const v4i16 lo = rd(lo_addr), hi = rd(hi_addr);
+      const i16x8 t8v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      return __builtin_bit_cast(bf16x8, t8v);
+    };
+    bf16x8 fz[2][4], fy[2][4], fb[2][4];
+    auto load_step = [&](auto ks_tag, bf16x8 (&dz_)[4], bf16x8 (&dy_)[4], bf16x8 (&db)[4]) {
+      constexpr int ks = decltype(ks_tag)::value;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        dz_[i] = rd2(azc[i] + (32 * ks) * 128, azc[i] + (32 * ks + 8) * 128);
+        dy_[i] = rd2(ayc[i] + (32 * ks) * 128, ayc[i] + (32 * ks + 8) * 128);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        db[j] = rd2(sbc[ks][0] + j * kPixB, sbc[ks][1] + j * kPixB);
+      }
+    };
+    load_step(std::integral_constant<int, 0>{}, fz[0], fy[0], fb[0]);
+    auto step = [&](auto ks_tag) {
+      constexpr int ks = decltype(ks_tag)::value;
+      if constexpr (ks + 1 < W_KS)
+        load_step(std::integral_constant<int, ks + 1>{}, fz[(ks + 1) & 1], fy[(ks + 1) & 1], fb[(ks + 1) & 1]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          accz[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fz[ks & 1][i], fb[ks & 1][j], accz[i][j], 0, 0, 0);
+          accy[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fy[ks & 1][i], fb[ks & 1][j], accy[i][j], 0, 0, 0);
+        }
+      if constexpr (ks + 1 < W_KS) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {  // 24 reads over 32 MFMAs
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    step(std::integral_constant<int, 0>{});
+    step(std::integral_constant<int, 1>{});
+    step(std::integral_constant<int, 2>{});
+    step(std::integral_constant<int, 3>{});
+    step(std::integral_constant<int, 4>{});
+    step(std::integral_constant<int, 5>{});
+    step(std::integral_constant<int, 6>{});
+    static_assert(W_KS == 7, "unrolled k-steps");
+  };
+
+  issue(t_begin, smem);  // the host launches no more blocks than tiles
+  pool_load(t_begin);
+  int cur = 0;
+  for (int t = t_begin; t < t_end; ++t) {
+    // stage `cur` and this tile's pooled vectors have landed; every wave is past
+    // the previous tile's MFMA loop (dz tile and stage cur ^ 1 are free)
+    vmcnt<0>();
+    raw_barrier();
+    // the compiler counts only its own loads: have it wait for the pooled vectors here,
+    // where they have landed, and not behind the copies issued next
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) asm volatile("" : "+v"(pg[it][rr][cc]), "+v"(pw[it][rr][cc]));
+    if (t + 1 < t_end) issue(t + 1, smem + (cur ^ 1) * W_BUF);
+    form(t, smem + cur * W_BUF);
+    if (t + 1 < t_end) pool_load(t + 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    raw_barrier();
+    mma_tile(cur);
+    cur ^= 1;
+  }
+  // partial [2][64 co][256]: row co = 16 i + 4 g + e, column = 64 wave + 16 j + (lane & 15)
+  float* pb = part + (int64_t)blockIdx.x * P_OUT;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int o = (16 * i + 4 * g + e) * kK + 64 * wave + 16 * j + (lane & 15);
+        pb[o] = accz[i][j][e];
+        pb[kCo * kK + o] = accy[i][j][e];
+      }
+  // BN-backward sums: lanes that share a channel vector (lane % 8), then the
+  // four waves in order, into one [2][64] partial row
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(smem + P_DZ);  // [2][4 waves][64]
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+      msum[c] += __shfl_xor(msum[c], off, 64);
+      msq[c] += __shfl_xor(msq[c], off, 64);
+    }
+  }
+  if (lane < 8)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      red[wave * kCo + 8 * lane + c] = msum[c];
+      red[(4 + wave) * kCo + 8 * lane + c] = msq[c];
+    }
+  __syncthreads();
+  if (tid < 2 * kCo) {
+    const int mo = tid / kCo, ch = tid % kCo;
+    const float* r = red + mo * 4 * kCo + ch;
+    mpart[((int64_t)mo * gridDim.x + blockIdx.x) * kCo + ch] = ((r[0] + r[kCo]) + r[2 * kCo]) + r[3 * kCo];
+  }
+}
+
 // out[e] = sum over nb partial rows (fixed order); block = 4 row groups x 64 x 4 columns
 template <typename OT>
 __global__ __launch_bounds__(256) void partial_sum_kernel(const float* __restrict__ part, int nb, int n,
@@ -523,6 +841,63 @@ at::Tensor stem_halo_wgrad(const at::Tensor& dy, const at::Tensor& s, int64_t ho
   }
   DMP_HIP_CHECK(hipGetLastError());
   return out;
+}
+
+// The stem's folded backward in one pass over y: dz = relu_mask(y) * maxpool_backward(dy) (3x3 / s2 pool,
+// pad 0 or 1) is formed per tile in LDS and never stored.  Returns
+//   t_dz = dz^T P, t_y = y^T P   fp32 [64, 256], bit-identical to stem_halo_wgrad(dz | y, s, ho, fp32)
+//   sums                         fp64 [129], maxpool2d_bn_backward's (sum dz, sum dz (y - mean), rows)
+// dy: pooled gradient [N, 64, Hp, Wp] channels_last bf16, idx its argmax bytes (maxpool2d_bn_forward),
+// y: the conv output [N, 64, ho, 112] channels_last bf16.
+std::vector<at::Tensor> stem_halo_wgrad_pool(const at::Tensor& dy, const at::Tensor& idx, const at::Tensor& y,
+                                             const at::Tensor& s, const at::Tensor& scale, const at::Tensor& shift,
+                                             const at::Tensor& mean, int64_t ho, int64_t pad) {
+  check_s(s, ho);
+  const int64_t n = s.size(0), hs = s.size(2);
+  TORCH_CHECK(ho >= 4 && ho % WR == 0 && (pad == 0 || pad == 1), "stem halo wgrad+pool: even Ho >= 4, pool pad 0 or 1");
+  const int64_t hp = (ho + 2 * pad - 3) / 2 + 1, wp = (kWo + 2 * pad - 3) / 2 + 1;
+  auto cl_bf16 = [&](const at::Tensor& t, int64_t h, int64_t w, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == s.device() && t.scalar_type() == at::kBFloat16 && t.dim() == 4 &&
+                    t.size(0) == n && t.size(1) == kCo && t.size(2) == h && t.size(3) == w &&
+                    t.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "stem halo wgrad+pool: ", name, " must be channels_last bf16 [", n, ", 64, ", h, ", ", w, "]");
+  };
+  cl_bf16(y, ho, kWo, "y");
+  cl_bf16(dy, hp, wp, "dy");
+  TORCH_CHECK(idx.is_cuda() && idx.device() == s.device() && idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                  idx.numel() == dy.numel(), "stem halo wgrad+pool: bad argmax tensor");
+  for (const auto* t : {&scale, &shift, &mean})
+    TORCH_CHECK(t->is_cuda() && t->device() == s.device() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->numel() == kCo, "stem halo wgrad+pool: BN coefficients must be contiguous fp32 [64]");
+  const int tpi = (int)(ho / WR);
+  const int tiles = (int)(n * tpi);
+  auto out = at::empty({2, kCo, kK}, s.options().dtype(at::kFloat));
+  auto sums = at::empty({2 * kCo + 1}, s.options().dtype(at::kDouble));
+  if (tiles == 0) {
+    out.zero_();
+    return {out[0], out[1], sums.zero_()};
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  const int grid = std::min(tiles, num_cus());
+  auto part = at::empty({(int64_t)grid * P_OUT}, s.options().dtype(at::kFloat));
+  auto mpart = at::empty({2, grid, kCo}, s.options().dtype(at::kFloat));
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const bf16*>(dy.data_ptr()),
+                       idx.data_ptr<uint8_t>(), reinterpret_cast<const bf16*>(y.data_ptr()),
+                       reinterpret_cast<const bf16*>(s.data_ptr()), scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       mean.data_ptr<float>(), part.data_ptr<float>(), mpart.data_ptr<float>(),
+                       moments_zero_target(sums.data_ptr<double>(), grid), (int)hs, (int)ho, (int)hp, (int)wp, tiles,
+                       tpi, (int64_t)s.numel() * 2);
+  };
+  if (pad == 1) launch(stem_wgrad_pool_kernel<1>);
+  else launch(stem_wgrad_pool_kernel<0>);
+  DMP_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(partial_sum_kernel<float>, dim3(P_OUT / 256), dim3(256), 0, stream, part.data_ptr<float>(), grid,
+                     P_OUT, out.data_ptr<float>());
+  DMP_HIP_CHECK(hipGetLastError());
+  bn_reduce_partials_launch(mpart.data_ptr<float>(), grid, kCo, sums.data_ptr<double>(), (double)(n * ho * kWo),
+                            stream);
+  return {out[0], out[1], sums};
 }
 
 

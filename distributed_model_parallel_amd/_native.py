@@ -95,6 +95,8 @@ FEATURES = {
     "bn_fold_ds": "downsample conv + BN folded into the same GEMM as bn3 (ops/bn_fold.py) -> separate shortcut",
     "fuse_stem_wgrad": "stem BN backward apply folded into the stem weight gradient (ops/fused.py) "
                        "-> the apply pass + one weight gradient",
+    "fuse_stem_pool_wgrad": "stem pool / ReLU backward formed inside the stem weight-gradient kernel "
+                            "(stem_halo.hip stem_halo_wgrad_pool) -> maxpool2d_bn_backward + two stem_halo_wgrad",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",
 }

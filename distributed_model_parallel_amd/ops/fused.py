@@ -326,8 +326,17 @@ class _StemBNReLUMaxPoolFn(torch.autograd.Function):
         reduce_grads, wdtype, has_w, has_b, pad, n, ho, wo, mdtype = ctx.meta
         co = y.shape[1]
         scale, shift, mean, invstd = (coef[i].contiguous() for i in range(4))
-        dz, sums = C.maxpool2d_bn_backward(dy.contiguous(memory_format=torch.channels_last), idx, y,
-                                           scale, shift, mean, 3, 2, pad)
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        if _FUSE_STEM_POOL_WGRAD:
+            # one pass over y: dz is formed per tile inside the weight-gradient kernel
+            # and never written (stem_halo.hip stem_halo_wgrad_pool)
+            t_dz, t_y, sums = C.stem_halo_wgrad_pool(dy, idx, y, s, scale, shift, mean, ho, pad)
+            _STATS_FUSED["stem_pool_wgrad"] += 1
+        else:
+            dz, sums = C.maxpool2d_bn_backward(dy, idx, y, scale, shift, mean, 3, 2, pad)
+            rows = lambda t: t.permute(0, 2, 3, 1).reshape(n * ho * wo, co)  # noqa: E731
+            t_dz = C.stem_halo_wgrad(rows(dz), s, ho, torch.float32)
+            t_y = C.stem_halo_wgrad(rows(y), s, ho, torch.float32)
         sums = sums[: 2 * co]
         local = sums
         if reduce_grads is not None:
@@ -335,9 +344,6 @@ class _StemBNReLUMaxPoolFn(torch.autograd.Function):
             sums = reduce_grads(sums)
         sdz, sdzx = sums[:co], sums[co:]
         istd = invstd.double()
-        rows = lambda t: t.permute(0, 2, 3, 1).reshape(n * ho * wo, co)  # noqa: E731
-        t_dz = C.stem_halo_wgrad(rows(dz), s, ho, torch.float32)
-        t_y = C.stem_halo_wgrad(rows(y), s, ho, torch.float32)
         # colsum(P)[r*64 + q*16 + ch] = sum over images and output pixels of s[n, ch, oh+r, ow+q]:
         # the batch sum of the (channels-last) s2d image as one column reduction; its 4 x 4
         # window sums (fp64), the BN-backward coefficients al / be / cc and
@@ -358,6 +364,7 @@ class _StemBNReLUMaxPoolFn(torch.autograd.Function):
 
 
 _STATS_FUSED["stem_bn_relu_maxpool"] = 0
+_STATS_FUSED["stem_pool_wgrad"] = 0  # backwards that took the one-pass stem_halo_wgrad_pool route
 
 
 def _stem_fold_ok(conv: nn.Module, x: torch.Tensor) -> bool:
@@ -410,3 +417,6 @@ from .. import _native as _nat  # noqa: E402
 _FUSE_STEM_POOL = not _nat.disabled("fuse_stem_pool")
 # DMP_DISABLE=fuse_stem_wgrad: keep the stem's BN backward apply pass (A/B runs)
 _FUSE_STEM_WGRAD = not _nat.disabled("fuse_stem_wgrad")
+# DMP_DISABLE=fuse_stem_pool_wgrad: the pool backward writes dz and the weight-gradient
+# kernel runs once on dz and once on y (A/B runs)
+_FUSE_STEM_POOL_WGRAD = not _nat.disabled("fuse_stem_pool_wgrad")

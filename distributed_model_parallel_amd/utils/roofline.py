@@ -82,6 +82,8 @@ def flops(name: str, args, kw) -> float:
             return 2.0 * a0.shape[0] * ho * ho * wm.shape[0] * wm.shape[1]
         if name == "stem_halo_wgrad":
             return 2.0 * _rows4(a0) * 64 * 256
+        if name == "stem_halo_wgrad_pool":  # dz^T P and y^T P; bytes are its operands (y, s, dy, idx)
+            return 2.0 * 2.0 * _rows4(_arg(args, kw, 2, "y")) * 64 * 256
         if name in ("attention_forward", "attention_backward"):
             b, s, h = (args[1], args[2], args[3]) if name == "attention_forward" else (args[4], args[5], args[6])
             f = 4.0 * b * h * s * s * 64

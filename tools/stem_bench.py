@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the ResNet stem passes at batch N: halo kernels (csrc/conv/stem_halo.hip)
-vs the row-tap implicit GEMM (conv_nt / conv_wgrad) vs MIOpen.  HIP events,
-median of 20.   python tools/stem_bench.py [--batch 2048]"""
+vs the row-tap implicit GEMM (conv_nt / conv_wgrad) vs MIOpen, and the folded
+backward in one pass (stem_halo_wgrad_pool) next to the three calls it
+replaces.  HIP events, median of 20.   python tools/stem_bench.py [--batch 2048]"""
 import argparse
 import os
 import sys
@@ -30,12 +31,26 @@ def main():
     s = C.space_to_depth2(x, 3)
     dy = torch.randn(n * 112 * 112, 64, device="cuda").bfloat16()
     dy4 = dy.view(n, 112, 112, 64).permute(0, 3, 1, 2)
+    # the folded backward's operands: a real argmax from the fused pool, a mixed ReLU mask
+    y4 = dy4  # any bf16 [N, 64, 112, 112] channels_last tensor serves as the conv output
+    sc = torch.rand(64, device="cuda") + 0.5
+    sh = torch.randn(64, device="cuda") * 0.1
+    mean = torch.zeros(64, device="cuda")
+    _, idx = C.maxpool2d_bn_forward(y4, sc, sh, 3, 2, 1)
+    dyp = torch.randn(n, 64, 56, 56, device="cuda").bfloat16().contiguous(memory_format=torch.channels_last)
+    dz = C.maxpool2d_bn_backward(dyp, idx, y4, sc, sh, mean, 3, 2, 1)[0]
+    dz2 = dz.permute(0, 2, 3, 1).reshape(n * 112 * 112, 64)
     rows = [
         ("s2d", lambda: C.space_to_depth2(x, 3)),
         ("fwd halo (+moments)", lambda: C.stem_halo_fwd(s, wm, 112, True)),
         ("fwd row-tap GEMM (+moments)", lambda: C.conv_nt(s, wm, 4, 1, 1, 0, 112, 112, mode="moments", kc=64)),
         ("fwd MIOpen", lambda: F.conv2d(x, w, None, 2, 3)),
         ("wgrad halo", lambda: C.stem_halo_wgrad(dy, s, 112, torch.bfloat16)),
+        ("folded bwd: pool/BN backward (writes dz)", lambda: C.maxpool2d_bn_backward(dyp, idx, y4, sc, sh, mean, 3, 2, 1)),
+        ("folded bwd: wgrad halo (dz, fp32)", lambda: C.stem_halo_wgrad(dz2, s, 112, torch.float32)),
+        ("folded bwd: wgrad halo (y, fp32)", lambda: C.stem_halo_wgrad(dy, s, 112, torch.float32)),
+        ("folded bwd: one pass (stem_halo_wgrad_pool, 2x FLOP)",
+         lambda: C.stem_halo_wgrad_pool(dyp, idx, y4, s, sc, sh, mean, 112, 1)),
         ("wgrad row-tap TN", lambda: C.conv_wgrad(dy, s, 4, 1, 1, 0, 112, 112, torch.bfloat16, kc=64)),
         ("wgrad MIOpen", lambda: torch.ops.aten.convolution_backward(
             dy4, x, w, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1, [False, True, False])),

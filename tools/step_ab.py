@@ -19,6 +19,7 @@ arms:
   f32c / f32t  BN-fold fp32 weights from the optimizer-driven cache / a cast per forward
   finf / finsep  BN-fold finalize fused into the folded-moments launch / a separate bn_finalize
   tnnarrow / tnwide  4-wave weight gradients with a side of 64 / 128 on narrow tiles / on 256 x 256
+  stemfused / stemsep  stem pool / ReLU backward formed inside the weight-gradient kernel / written as dz + two weight gradients
   n128 / miopen  Cout = 128 3x3 forwards (ResNet-50 layer-2 stride 2) on the 4-wave 256 x 128 tile / MIOpen
 
   python tools/step_ab.py --model vit_b_16 --batch 256 --arms plain_fwd,plain_xl [--steps 10] [--rounds 3]
@@ -31,7 +32,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_model_parallel_amd import _native  # noqa: E402
-from distributed_model_parallel_amd.ops import bn_fold, conv1x1, conv_igemm, linear, wt_cache  # noqa: E402
+from distributed_model_parallel_amd.ops import bn_fold, conv1x1, conv_igemm, fused, linear, wt_cache  # noqa: E402
 from distributed_model_parallel_amd.train.step import StepConfig, build_train_state  # noqa: E402
 from distributed_model_parallel_amd.utils.env import init_distributed, destroy_distributed  # noqa: E402
 
@@ -75,6 +76,8 @@ def _arm(name):
         "finsep": lambda: setattr(bn_fold, "_FUSED_FINALIZE", False),
         "tnnarrow": lambda: C.set_tn_narrow(True),
         "tnwide": lambda: C.set_tn_narrow(False),
+        "stemfused": lambda: setattr(fused, "_FUSE_STEM_POOL_WGRAD", True),
+        "stemsep": lambda: setattr(fused, "_FUSE_STEM_POOL_WGRAD", False),
     }
     return table[name]
 
