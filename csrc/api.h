@@ -66,6 +66,17 @@ std::vector<at::Tensor> bn_backward_apply(const at::Tensor& dy, const at::Tensor
                                           const c10::optional<at::Tensor>& acc_bias);
 void set_bn_streaming(bool on);
 
+// ---- bn/bn_apply_gram.hip ----
+bool bn_apply_gram_supported(int64_t C);
+std::vector<at::Tensor> bn_forward_apply_gram(const at::Tensor& x, const at::Tensor& sums,
+                                              const c10::optional<at::Tensor>& weight,
+                                              const c10::optional<at::Tensor>& bias,
+                                              const c10::optional<at::Tensor>& running_mean,
+                                              const c10::optional<at::Tensor>& running_var, double momentum,
+                                              double eps, int64_t C,
+                                              const c10::optional<at::Tensor>& num_batches_tracked, double clip);
+void set_bn_gram_blocks(int64_t n);
+
 // ---- bn/bn_fold.hip ----
 bool bn_fold_supported(int64_t cout, int64_t cin);
 std::vector<at::Tensor> bn_fold_fwd(const at::Tensor& W, const at::Tensor& G, const at::Tensor& asums,

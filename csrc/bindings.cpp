@@ -22,6 +22,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_batches_tracked") = py::none(), py::arg("out_moments") = false,
         py::arg("clip") = INFINITY,
         py::call_guard<py::gil_scoped_release>());
+  m.def("bn_forward_apply_gram", &dmp::bn_forward_apply_gram, py::arg("x"), py::arg("sums"), py::arg("weight"),
+        py::arg("bias"), py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        py::arg("C"), py::arg("num_batches_tracked") = py::none(), py::arg("clip") = INFINITY,
+        "training-mode BN + ReLU apply that also returns the column moments and the fp32 Gram of its output",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bn_apply_gram_supported", &dmp::bn_apply_gram_supported);
+  m.def("set_bn_gram_blocks", &dmp::set_bn_gram_blocks);
   m.def("bn_eval_apply", &dmp::bn_eval_apply, py::arg("x"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("residual"),
         py::arg("relu"), py::arg("C"), py::arg("clip") = INFINITY,

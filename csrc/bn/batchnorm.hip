@@ -35,6 +35,7 @@
 #include "../api.h"
 #include "../common.h"
 #include "../launch.h"
+#include "bn_coeffs.h"
 
 namespace dmp {
 namespace {
@@ -200,22 +201,7 @@ __global__ __launch_bounds__(kThreads) void bn_moments_kernel(
   block_combine_store<VEC>(s, q, L, C, part);
 }
 
-// Per-channel forward coefficients from (possibly all-reduced) moments.
-__device__ __forceinline__ void fwd_coeffs(const double* __restrict__ sums, int C, int c,
-                                           const float* __restrict__ w, const float* __restrict__ b,
-                                           float eps, float& mean, float& invstd, float& var_b,
-                                           float& scale, float& shift) {
-  const double n = sums[2 * C];
-  const double m = sums[c] / n;
-  double v = sums[C + c] / n - m * m;
-  v = v < 0.0 ? 0.0 : v;
-  mean = (float)m;
-  var_b = (float)v;
-  invstd = (float)(1.0 / sqrt(v + (double)eps));
-  const float ww = w ? w[c] : 1.f, bb = b ? b[c] : 0.f;
-  scale = ww * invstd;
-  shift = bb - mean * scale;
-}
+// (fwd_coeffs, the per-channel forward coefficients: bn_coeffs.h)
 
 // Coefficients only (no pass over x): when the BN apply + ReLU is fused into
 // the consuming GEMM's operand staging (ops/fused.py bn_relu_conv1x1), the BN
@@ -589,6 +575,9 @@ float* fptr(const c10::optional<at::Tensor>& t) {
 }
 
 }  // namespace
+
+// The apply passes' streaming policy, for bn_apply_gram.hip.
+bool bn_streaming(int64_t M, int64_t C) { return streaming(M, C); }
 
 // Shared with the GEMM moments epilogue (csrc/conv/gemm_bf16.hip).
 void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,

@@ -14,6 +14,8 @@ namespace dmp {
 // [2C+1] moments (the zeroing contract is in common.h)
 void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
                                hipStream_t stream);
+// whether an apply pass over [M, C] bf16 uses non-temporal accesses (set_bn_streaming)
+bool bn_streaming(int64_t M, int64_t C);
 
 // conv/gemm_bf16.hip: the split-M partials of a TN GEMM summed into `out`
 // (acc: added to it), and the validated accumulation target of a weight

@@ -93,6 +93,8 @@ FEATURES = {
     "rowtap_stem": "row-tap stem implicit GEMM (stem.hip) -> MIOpen",
     "bn_fold": "bottleneck bn3 folded through conv3 (ops/bn_fold.py) -> conv + BN apply passes",
     "bn_fold_ds": "downsample conv + BN folded into the same GEMM as bn3 (ops/bn_fold.py) -> separate shortcut",
+    "fuse_bn_gram": "the bn3 fold's Gram a2^T a2 formed inside bn2's apply pass (bn_apply_gram.hip) "
+                    "-> the apply pass + a TN GEMM over its output",
     "fuse_stem_wgrad": "stem BN backward apply folded into the stem weight gradient (ops/fused.py) "
                        "-> the apply pass + one weight gradient",
     "fuse_stem_pool_wgrad": "stem pool / ReLU backward formed inside the stem weight-gradient kernel "

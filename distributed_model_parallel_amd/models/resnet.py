@@ -116,10 +116,12 @@ class Bottleneck(nn.Module):
                 raw, sums2 = self.conv2.forward_with_moments(out)
             else:
                 raw, sums2 = self.conv2(out), None
-            a2, asums = self.bn2(raw, sums=sums2, out_moments=True)
+            # ... and, where the fused kernel covers it, the Gram a2^T a2 the fold needs
+            a2, asums, gram = self.bn2(raw, sums=sums2, out_gram=True)
             if fold_ds:
-                return conv1x1_bn_fold(self.conv3, self.bn3, a2, asums, downsample=self.downsample, x=xt)
-            return conv1x1_bn_fold(self.conv3, self.bn3, a2, asums, identity)
+                return conv1x1_bn_fold(self.conv3, self.bn3, a2, asums, downsample=self.downsample, x=xt,
+                                       a_gram=gram)
+            return conv1x1_bn_fold(self.conv3, self.bn3, a2, asums, identity, a_gram=gram)
         out = conv_bn(self.conv2, self.bn2, out)
         return conv_bn(self.conv3, self.bn3, out, identity)
 

@@ -40,6 +40,22 @@ ACTS = {None: None, "relu": _INF, "relu6": 6.0}
 # epilogue (BnBwdSlot); DMP_DISABLE=fuse_bn_bwd turns it off for A/B runs.
 _FUSE_BWD = not _native.disabled("fuse_bn_bwd")
 
+# The Gram matrix a^T a of a BN + ReLU output formed inside its apply pass
+# (csrc/bn/bn_apply_gram.hip) for the bn3 fold (ops/bn_fold.py), instead of a
+# TN GEMM that reads the output again; DMP_DISABLE=fuse_bn_gram restores the two
+# launches.  _GRAM_FUSE_C: the widths routed to it (tools/step_ab.py arms
+# gram* set it per width).
+_FUSE_GRAM = not _native.disabled("fuse_bn_gram")
+_GRAM_FUSE_C = (64, 128, 256)
+_STATS["fused_gram"] = 0
+
+
+def _gram_fused_ok(x2: torch.Tensor, res2, relu: bool, rm) -> bool:
+    """The fused apply + Gram kernel's conditions (native path already chosen)."""
+    return (_FUSE_GRAM and relu and res2 is None and x2.dtype == torch.bfloat16
+            and x2.shape[1] in _GRAM_FUSE_C and x2.shape[0] > 0 and not in_recompute()
+            and (rm is None or rm.dtype == torch.float32))
+
 
 def stats() -> dict:
     return dict(_STATS)
@@ -86,23 +102,33 @@ def local_moments(x2: torch.Tensor, native: bool) -> torch.Tensor:
 
 
 def forward_apply(x2, sums, weight, bias, rm, rv, momentum, eps, res2, relu, native, nbt=None,
-                  out_moments=False, clip=_INF):
+                  out_moments=False, clip=_INF, out_gram=False):
     """Training-mode normalise from (global) moments; updates running stats and
     increments `nbt` (num_batches_tracked) -- inside the kernel when native.
 
-    Returns (y, mean, invstd) [+ fp64 (colsum y, colsum y^2, rows) with out_moments]."""
+    Returns (y, mean, invstd) [+ fp64 (colsum y, colsum y^2, rows) with out_moments]
+    [+ the Gram y^T y with out_gram (implies out_moments): fp32 from the fused
+    native kernel, None where that kernel does not apply (the caller forms it),
+    fp64 on the torch path]."""
     c = x2.shape[1]
+    out_moments = out_moments or out_gram
     if native:
-        return _native.require("bn").bn_forward_apply(x2, sums, weight, bias, rm, rv,
-                                                       float(momentum), float(eps), res2, relu, c,
-                                                       nbt, out_moments, clip)
+        C = _native.require("bn")
+        if out_gram and _gram_fused_ok(x2, res2, relu, rm):
+            _STATS["fused_gram"] += 1
+            return C.bn_forward_apply_gram(x2, sums, weight, bias, rm, rv, float(momentum), float(eps), c,
+                                           nbt, clip)
+        res = C.bn_forward_apply(x2, sums, weight, bias, rm, rv, float(momentum), float(eps), res2, relu, c,
+                                 nbt, out_moments, clip)
+        return list(res) + [None] if out_gram else res
     if nbt is not None:
         nbt.add_(1)
     mean, invstd, scale, shift = _finalize_torch(sums, weight, bias, rm, rv, momentum, eps)
     y = _apply_torch(x2, scale, shift, res2, relu, clip)
     if out_moments:
         yd = y.double()
-        return [y, mean, invstd, torch.cat([yd.sum(0), (yd * yd).sum(0), yd.new_tensor([float(y.shape[0])])])]
+        res = [y, mean, invstd, torch.cat([yd.sum(0), (yd * yd).sum(0), yd.new_tensor([float(y.shape[0])])])]
+        return res + [yd.t() @ yd] if out_gram else res
     return [y, mean, invstd]
 
 
@@ -250,7 +276,8 @@ class _BatchNormActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps,
                 act_clip, reduce_moments, reduce_grads, pre_sums=None, nbt=None, bwd_slot=None,
-                out_moments=False):
+                out_moments=False, out_gram=False):
+        out_moments = out_moments or out_gram
         relu = act_clip is not None
         clip = act_clip if relu else _INF
         x2, back = _as_rows(x)
@@ -272,9 +299,10 @@ class _BatchNormActFn(torch.autograd.Function):
             upd_rm = running_mean if (running_mean is not None and running_mean.dtype == torch.float32) else None
             upd_rv = running_var if upd_rm is not None else None
             res = forward_apply(x2, sums, w32, b32, upd_rm, upd_rv, momentum, eps, res2, relu, native, nbt,
-                                out_moments, clip)
+                                out_moments, clip, out_gram)
             y2, mean, invstd = res[0], res[1], res[2]
             osums = res[3] if out_moments else None
+            gram = res[4] if out_gram else None
             if running_mean is not None and upd_rm is None:  # low-precision buffers
                 c = x2.shape[1]
                 n = sums[2 * c]
@@ -285,7 +313,7 @@ class _BatchNormActFn(torch.autograd.Function):
             count = torch.full((1,), float(x2.shape[0]), dtype=torch.float64, device=x2.device)
             y2, mean, invstd = eval_apply(x2, running_mean, running_var, w32, b32, eps, res2, relu,
                                           native, clip)
-            osums = None
+            osums = gram = None
         # the ReLU mask needs the output only when a residual was added before the
         # ReLU; otherwise backward re-derives it from x (one tensor read fewer)
         ctx.save_for_backward(x2, y2 if (relu and residual is not None) else None, w32, b32, mean,
@@ -305,16 +333,21 @@ class _BatchNormActFn(torch.autograd.Function):
             if osums is None:  # eval mode: moments of the output on request all the same
                 yd = y2.double()
                 osums = torch.cat([yd.sum(0), (yd * yd).sum(0), yd.new_tensor([float(y2.shape[0])])])
-            ctx.mark_non_differentiable(osums)
+            if out_gram and gram is None and not native:  # eval mode on the torch path
+                yd = y2.double()
+                gram = yd.t() @ yd
+            ctx.mark_non_differentiable(*([osums] if gram is None else [osums, gram]))
             # osums never gets a gradient: no zero [2C+1] fp64 fill per backward
             ctx.set_materialize_grads(False)
+            if out_gram:  # gram None: the native kernel does not cover this call
+                return back(y2), osums, gram
             return back(y2), osums
         return back(y2)
 
     @staticmethod
-    def backward(ctx, dy, _dosums=None):
+    def backward(ctx, dy, _dosums=None, _dgram=None):
         if dy is None:
-            return (None,) * 16
+            return (None,) * 17
         x2, y2, w32, b32, mean, invstd, count = ctx.saved_tensors
         (native, training, relu, has_res, back, has_w, has_b, reduce_grads, wdtype,
          ndim, clip) = ctx.meta
@@ -359,7 +392,7 @@ class _BatchNormActFn(torch.autograd.Function):
         gres = back(dres2) if has_res else None
         gw = dw.to(wdtype) if has_w and ctx.needs_input_grad[2] and acc_w is None else None
         gb = db.to(wdtype) if has_b and ctx.needs_input_grad[3] and acc_b is None else None
-        return gx, gres, gw, gb, None, None, None, None, None, None, None, None, None, None, None, None
+        return (gx, gres, gw, gb) + (None,) * 13
 
 
 def batch_norm_act(x: torch.Tensor, running_mean: Optional[torch.Tensor],
@@ -370,12 +403,16 @@ def batch_norm_act(x: torch.Tensor, running_mean: Optional[torch.Tensor],
                    reduce_grads: Optional[GradReducer] = None,
                    sums: Optional[torch.Tensor] = None,
                    num_batches_tracked: Optional[torch.Tensor] = None,
-                   out_moments: bool = False, act: Optional[str] = "_from_relu"):
+                   out_moments: bool = False, act: Optional[str] = "_from_relu", out_gram: bool = False):
     """Functional fused BN(+residual)(+ReLU).  `sums`: precomputed local moments
     [2C+1] of `x` (from a fused conv epilogue); ignored in eval mode.
     `num_batches_tracked`: incremented once (training mode), in-kernel when native.
     `out_moments`: also return the fp64 [2C+1] (colsum, colsum of squares, rows)
     of the OUTPUT, reduced inside the apply pass (ops/bn_fold.py needs colsum).
+    `out_gram`: return (out, moments, G) with G = out^T out over the [M, C] rows
+    (non-differentiable, like the moments): fp32 formed inside the native apply
+    pass where bn_apply_gram.hip covers the call, None on the GPU where it does
+    not (the caller forms it), fp64 on the torch path.
     `act`: None / "relu" / "relu6" (overrides `relu` when given)."""
     if act == "_from_relu":
         act = "relu" if relu else None
@@ -388,12 +425,16 @@ def batch_norm_act(x: torch.Tensor, running_mean: Optional[torch.Tensor],
         slot = BnBwdSlot()
     out = _BatchNormActFn.apply(x, residual, weight, bias, running_mean, running_var, training,
                                 momentum, eps, clip, reduce_moments, reduce_grads, sums,
-                                num_batches_tracked if training else None, slot, out_moments)
-    osums = None
-    if out_moments:
+                                num_batches_tracked if training else None, slot, out_moments, out_gram)
+    osums = gram = None
+    if out_gram:
+        out, osums, gram = out
+    elif out_moments:
         out, osums = out
     if slot is not None and slot.x2 is not None:
         out._dmp_bnbwd = slot  # a native 1x1 conv consuming `out` may fuse our backward reductions
+    if out_gram:
+        return out, osums, gram
     return (out, osums) if out_moments else out
 
 
@@ -425,7 +466,7 @@ class BatchNormAct2d(nn.BatchNorm2d):
         return None, None
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None,
-                sums: Optional[torch.Tensor] = None, out_moments: bool = False):
+                sums: Optional[torch.Tensor] = None, out_moments: bool = False, out_gram: bool = False):
         self._check_input_dim(x)
         use_batch = self.training or not self.track_running_stats
         recompute = in_recompute()  # activation-checkpoint recompute: no second stat update
@@ -448,7 +489,7 @@ class BatchNormAct2d(nn.BatchNorm2d):
                               residual=residual, reduce_moments=rmom, reduce_grads=rgrad,
                               sums=sums if use_batch else None,
                               num_batches_tracked=nbt if use_batch else None,
-                              out_moments=out_moments)
+                              out_moments=out_moments, out_gram=out_gram)
 
     def extra_repr(self) -> str:
         return super().extra_repr() + (f", act={self.act}" if self.act else "")

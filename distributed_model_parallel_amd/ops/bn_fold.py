@@ -46,7 +46,7 @@ import torch.nn as nn
 from .. import _native
 from . import wt_cache
 
-_STATS = {"fold": 0, "fold_fused_bwd": 0, "fold_bnbwd_epilogue": 0}
+_STATS = {"fold": 0, "fold_fused_bwd": 0, "fold_bnbwd_epilogue": 0, "fold_gram_given": 0}
 ENABLED = not _native.disabled("bn_fold")
 
 
@@ -133,13 +133,14 @@ class _ConvBNFoldFn(torch.autograd.Function):
     BNs folded (module docstring)."""
 
     @staticmethod
-    def forward(ctx, meta, a, a_sums, w3, g3, b3, x, wd, gd, bd, residual):
+    def forward(ctx, meta, a, a_sums, w3, g3, b3, x, wd, gd, bd, residual, a_gram=None):
         native = _native.gpu_path(a)
         C = _native.require("bn_fold") if native else None
         n, cin, h, w = a.shape
         cout = w3.shape[0]
         a2 = _rows(a)
-        br = [dict(inp=a2, asums=a_sums, W=w3.reshape(cout, cin), Wp=w3, g=g3, b=b3, spec=meta.bn[0], geom=[])]
+        br = [dict(inp=a2, asums=a_sums, W=w3.reshape(cout, cin), Wp=w3, g=g3, b=b3, spec=meta.bn[0], geom=[],
+                   gram=a_gram)]
         if x is not None:
             cx, hi, wi = x.shape[1], x.shape[2], x.shape[3]
             from .conv1x1 import _geom
@@ -202,7 +203,7 @@ class _ConvBNFoldFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        nret = 11
+        nret = 12
         if dout is None:
             return (None,) * nret
         a, x, w3, wd, out2 = ctx.saved_tensors[:5]
@@ -263,7 +264,7 @@ class _ConvBNFoldFn(torch.autograd.Function):
             if ctx.needs_input_grad[6]:
                 dx = _fold_shortcut_dgrad(meta, C, dz2, _rows(x), x.shape, gd_, ctx.geoms[1], native, n)
         gres = _unrows(dz2, n, h, w) if (ctx.has_res and ctx.needs_input_grad[10]) else None
-        return None, da, None, dw3, gg3, gb3, dx, dwd, ggd, gbd, gres
+        return None, da, None, dw3, gg3, gb3, dx, dwd, ggd, gbd, gres, None
 
 
 def _cpu_moments(x2: torch.Tensor) -> torch.Tensor:
@@ -293,7 +294,12 @@ def _fold_branch_forward(C, b, n, native):
     W, asums, geom = b["W"], b["asums"], b["geom"]
     cout, cin = W.shape
     rm, rv, momentum, eps, nbt, rmom, _ = b["spec"]
-    G = _gram(C, b["inp"], geom, native, n)
+    # branch 0's Gram may come out of the producing BN's apply pass (a_gram)
+    G = b.get("gram")
+    if G is None:
+        G = _gram(C, b["inp"], geom, native, n)
+    else:
+        _STATS["fold_gram_given"] += 1
     w32 = b["g"].float() if b["g"] is not None else None
     b32 = b["b"].float() if b["b"] is not None else None
     rm = rm if (rm is not None and rm.dtype == torch.float32) else None
@@ -441,14 +447,17 @@ def foldable(conv: nn.Module, bn: nn.Module, a: torch.Tensor) -> bool:
 
 def conv1x1_bn_fold(conv: nn.Module, bn: nn.Module, a: torch.Tensor, a_sums: torch.Tensor,
                     residual: Optional[torch.Tensor] = None, force: bool = False,
-                    downsample: Optional[nn.Module] = None, x: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    downsample: Optional[nn.Module] = None, x: Optional[torch.Tensor] = None,
+                    a_gram: Optional[torch.Tensor] = None) -> torch.Tensor:
     """relu(bn(conv(a)) + residual) with the BN folded through the GEMM, or --
     with ``downsample`` (Sequential(Conv1x1(stride s), BatchNormAct2d)) and the
     block input ``x`` instead of ``residual`` -- relu(bn(conv(a)) +
     bn_d(conv_d(x))) with both BNs folded into one GEMM over [a | x_s].
 
     ``a_sums``: fp64 [2Cin+1] (colsum a, colsum a^2, rows) -- from the producing
-    BN apply (``BatchNormAct2d(..., out_moments=True)``).  ``force`` runs the
+    BN apply (``BatchNormAct2d(..., out_moments=True)``).  ``a_gram``: a^T a
+    [Cin, Cin] over the rows of ``a`` when that apply pass formed it too
+    (``out_gram=True``); without it the fold runs its own Gram GEMM.  ``force`` runs the
     fold on any device (the CPU path is the same algebra in fp64: tests)."""
     if not (force or foldable(conv, bn, a)):
         raise RuntimeError("conv1x1_bn_fold: configuration not covered (check foldable())")
@@ -468,7 +477,7 @@ def conv1x1_bn_fold(conv: nn.Module, bn: nn.Module, a: torch.Tensor, a_sums: tor
                      x_park=getattr(x, "_dmp_gradslot", None) if two else None)
     out = _ConvBNFoldFn.apply(meta, a, a_sums, conv.weight, bn.weight, bn.bias, x if two else None,
                               cd.weight if two else None, bd.weight if two else None, bd.bias if two else None,
-                              residual)
+                              residual, a_gram)
     if meta.out_slot is not None and meta.out_slot.ready():
         out._dmp_bnbwd = meta.out_slot  # the next 1x1 conv's dgrad epilogue masks dz and reduces sum dz
     return out

@@ -20,6 +20,8 @@ arms:
   finf / finsep  BN-fold finalize fused into the folded-moments launch / a separate bn_finalize
   tnnarrow / tnwide  4-wave weight gradients with a side of 64 / 128 on narrow tiles / on 256 x 256
   stemfused / stemsep  stem pool / ReLU backward formed inside the weight-gradient kernel / written as dz + two weight gradients
+  gramfused / gramsep  the bn3 fold's Gram formed inside bn2's apply pass at every covered width / by the TN GEMM
+  gram64 / gram128 / gram256 / gram64_128  ... inside the apply pass at these widths only
   n128 / miopen  Cout = 128 3x3 forwards (ResNet-50 layer-2 stride 2) on the 4-wave 256 x 128 tile / MIOpen
 
   python tools/step_ab.py --model vit_b_16 --batch 256 --arms plain_fwd,plain_xl [--steps 10] [--rounds 3]
@@ -32,7 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_model_parallel_amd import _native  # noqa: E402
-from distributed_model_parallel_amd.ops import bn_fold, conv1x1, conv_igemm, fused, linear, wt_cache  # noqa: E402
+from distributed_model_parallel_amd.ops import batchnorm, bn_fold, conv1x1, conv_igemm, fused, linear, wt_cache  # noqa: E402
 from distributed_model_parallel_amd.train.step import StepConfig, build_train_state  # noqa: E402
 from distributed_model_parallel_amd.utils.env import init_distributed, destroy_distributed  # noqa: E402
 
@@ -78,6 +80,12 @@ def _arm(name):
         "tnwide": lambda: C.set_tn_narrow(False),
         "stemfused": lambda: setattr(fused, "_FUSE_STEM_POOL_WGRAD", True),
         "stemsep": lambda: setattr(fused, "_FUSE_STEM_POOL_WGRAD", False),
+        "gramfused": lambda: setattr(batchnorm, "_GRAM_FUSE_C", (64, 128, 256)),
+        "gramsep": lambda: setattr(batchnorm, "_GRAM_FUSE_C", ()),
+        "gram64": lambda: setattr(batchnorm, "_GRAM_FUSE_C", (64,)),
+        "gram128": lambda: setattr(batchnorm, "_GRAM_FUSE_C", (128,)),
+        "gram256": lambda: setattr(batchnorm, "_GRAM_FUSE_C", (256,)),
+        "gram64_128": lambda: setattr(batchnorm, "_GRAM_FUSE_C", (64, 128)),
     }
     return table[name]
 
