@@ -196,7 +196,8 @@ at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, co
 // ---- gemm/gemm_xl.hip (NT: host side; kernels in gemm_xl_nt8.hip, gemm_xl_w4.hip, gemm_xl_x2.hip) ----
 at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& mode,
                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& aux,
-                   const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& out);
+                   const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& out,
+                   const c10::optional<at::Tensor>& row_scale = c10::nullopt, int64_t rows_per_sample = 0);
 std::vector<at::Tensor> gemm_xl_dgelu_bgrad(const at::Tensor& A, const at::Tensor& B, const at::Tensor& aux);
 std::vector<at::Tensor> gemm_xl_conv(const at::Tensor& A, const at::Tensor& B, const std::string& mode,
                                      const c10::optional<at::Tensor>& residual,
@@ -243,6 +244,8 @@ void set_tn_narrow(bool on);
 bool colsum_supported(int64_t N);
 at::Tensor bias_grad(const at::Tensor& dy, at::ScalarType out_dtype);
 std::vector<at::Tensor> gelu_bwd_bias_grad(const at::Tensor& dy, const at::Tensor& h, at::ScalarType out_dtype);
+std::vector<at::Tensor> rowscale_bias_grad(const at::Tensor& dy, const at::Tensor& row_scale, int64_t rows_per_sample,
+                                           at::ScalarType out_dtype);
 
 // ---- loss/cross_entropy.hip ----
 std::vector<at::Tensor> cross_entropy_fwd(const at::Tensor& x, const at::Tensor& target,

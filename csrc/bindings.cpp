@@ -118,7 +118,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ---- large-tile transformer GEMM with fused bias / GELU / residual epilogues ----
   m.def("gemm_xl", &dmp::gemm_xl, py::arg("A"), py::arg("B"), py::arg("mode") = "store",
         py::arg("bias") = py::none(), py::arg("aux") = py::none(),
-        py::arg("residual") = py::none(), py::arg("out") = py::none(),
+        py::arg("residual") = py::none(), py::arg("out") = py::none(), py::kw_only(),
+        py::arg("row_scale") = py::none(), py::arg("rows_per_sample") = 0,
         py::call_guard<py::gil_scoped_release>());
   m.def("conv_xl", &dmp::conv_xl, py::arg("x"), py::arg("wmat"), py::arg("kh"), py::arg("kw"),
         py::arg("stride"), py::arg("pad"), py::arg("ho"), py::arg("wo"), py::arg("mode") = "moments",
@@ -267,6 +268,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("gelu_bwd_bias_grad", &dmp::gelu_bwd_bias_grad, py::arg("dy"), py::arg("h"), py::arg("out_dtype"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("rowscale_bias_grad", &dmp::rowscale_bias_grad, py::arg("dy"), py::arg("row_scale"),
+        py::arg("rows_per_sample"), py::arg("out_dtype"), py::call_guard<py::gil_scoped_release>());
 
   // ---- LayerNorm (last dim) ----
   m.def("layernorm_forward", &dmp::layernorm_forward,

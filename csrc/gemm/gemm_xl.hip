@@ -125,7 +125,7 @@ int g_xl_x2 = 1;
 
 // (conv epilogues of a plain GEMM only: the implicit-GEMM gather has no x2 form)
 bool use_x2(const XlArgs& a, int epi) {
-  if (epi < XL_MOMENTS || a.cv.cin > 0) return false;
+  if (is_linear_epi(epi) || a.cv.cin > 0) return false;
   if (g_xl_x2 == 0 || a.N % X2_BN != 0) return false;
   return g_xl_x2 == 2 || a.N % 256 != 0;
 }
@@ -163,7 +163,7 @@ void xl_launch(XlArgs a, int epi, int bn, hipStream_t s) {
   if (use_x2(a, epi)) return launch_xl_x2(a, epi, s);
   const int tbm = (bn == 256 && a.bm > 0) ? a.bm : XBM;
   const int blocks = ((a.M + tbm - 1) / tbm) * ((a.N + bn - 1) / bn);
-  const int ring = (g_xl_pipe == 0 && epi < XL_MOMENTS) ? 0 : 1;
+  const int ring = (g_xl_pipe == 0 && is_linear_epi(epi)) ? 0 : 1;
   if (bn == 128) return launch_xl_nt8(a, epi, 128, ring, blocks, s);
   if (g_xl_pipe >= 10 || a.cv.cin > 0) {
     a.tdbg = g_xl_tdbg;
@@ -203,7 +203,7 @@ constexpr unsigned epi_bit(int e) { return 1u << e; }
 int xl_mode(const std::string& mode, unsigned accept, const char* who) {
   static const struct { const char* name; int epi; } kModes[] = {
       {"store", XL_STORE}, {"bias", XL_BIAS}, {"bias_gelu", XL_BIAS_GELU}, {"dgelu", XL_DGELU},
-      {"bias_res", XL_BIAS_RES}, {"moments", XL_MOMENTS}, {"add", XL_ADD}, {"bnbwd", XL_BNBWD},
+      {"bias_res", XL_BIAS_RES}, {"bias_res_scale", XL_BIAS_RES_SCALE}, {"moments", XL_MOMENTS}, {"add", XL_ADD}, {"bnbwd", XL_BNBWD},
       {"affine", XL_AFFINE}};
   int epi = -1;
   for (const auto& m : kModes)
@@ -214,11 +214,14 @@ int xl_mode(const std::string& mode, unsigned accept, const char* who) {
 
 }  // namespace
 
-// C = epi(A @ B^T).  mode: "store" | "bias" | "bias_gelu" | "dgelu" | "bias_res".
+// C = epi(A @ B^T).  mode: "store" | "bias" | "bias_gelu" | "dgelu" | "bias_res" |
+// "bias_res_scale" (bias_res with the branch scaled per sample: row m takes
+// row_scale[m / rows_per_sample]).
 // Returns C ("bias_gelu": also fills aux with the pre-activation).
 at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& mode,
                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& aux,
-                   const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& out) {
+                   const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& out,
+                   const c10::optional<at::Tensor>& row_scale, int64_t rows_per_sample) {
   check_bf16_2d(A, "A");
   check_bf16_2d(B, "B");
   const int64_t M = A.size(0), K = A.size(1), N = B.size(0);
@@ -228,7 +231,7 @@ at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& 
   TORCH_CHECK(M > 0 && M < (1LL << 31) && N < (1LL << 31), "gemm_xl: size out of range");
   TORCH_CHECK(A.device() == B.device(), "gemm_xl: device mismatch");
   const int epi = xl_mode(mode, epi_bit(XL_STORE) | epi_bit(XL_BIAS) | epi_bit(XL_BIAS_GELU) | epi_bit(XL_DGELU) |
-                                    epi_bit(XL_BIAS_RES), "gemm_xl");
+                                    epi_bit(XL_BIAS_RES) | epi_bit(XL_BIAS_RES_SCALE), "gemm_xl");
   at::Tensor C;
   if (out) {
     C = *out;
@@ -238,7 +241,7 @@ at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& 
     C = at::empty({M, N}, A.options());
   }
   XlArgs a = xl_operands(A, A.stride(0), B, M, N, K, C);
-  if (epi == XL_BIAS || epi == XL_BIAS_GELU || epi == XL_BIAS_RES) {
+  if (epi == XL_BIAS || epi == XL_BIAS_GELU || epi == XL_BIAS_RES || epi == XL_BIAS_RES_SCALE) {
     TORCH_CHECK(bias && bias->scalar_type() == at::kBFloat16 && bias->numel() == N && bias->is_contiguous(),
                 "gemm_xl: bias must be a contiguous bf16 [N]");
     a.bias = bf16_ptr(*bias);
@@ -250,12 +253,24 @@ at::Tensor gemm_xl(const at::Tensor& A, const at::Tensor& B, const std::string& 
     a.aux = const_cast<bf16*>(bf16_ptr(*aux));
     a.ldaux = aux->stride(0);
   }
-  if (epi == XL_BIAS_RES) {
-    TORCH_CHECK(residual.has_value(), "gemm_xl: bias_res needs residual");
+  if (epi == XL_BIAS_RES || epi == XL_BIAS_RES_SCALE) {
+    TORCH_CHECK(residual.has_value(), "gemm_xl: ", mode, " needs residual");
     check_bf16_2d(*residual, "residual");
     TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemm_xl: residual shape");
     a.R = bf16_ptr(*residual);
     a.ldr = residual->stride(0);
+  }
+  if (epi == XL_BIAS_RES_SCALE) {
+    TORCH_CHECK(given(row_scale) && row_scale->is_cuda() && row_scale->device() == A.device() &&
+                    row_scale->scalar_type() == at::kFloat && row_scale->is_contiguous(),
+                "gemm_xl: row_scale must be a contiguous fp32 tensor on A's device");
+    TORCH_CHECK(rows_per_sample > 0, "gemm_xl: rows_per_sample must be positive");
+    TORCH_CHECK(row_scale->numel() * rows_per_sample == M, "gemm_xl: M (", M, ") must be row_scale.numel() (",
+                row_scale->numel(), ") * rows_per_sample (", rows_per_sample, ")");
+    a.rscale = row_scale->data_ptr<float>();
+    a.rows_per_sample = (int)rows_per_sample;
+  } else {
+    TORCH_CHECK(!given(row_scale), "gemm_xl: row_scale is for mode bias_res_scale only");
   }
   const int bn = pick_bn((int)M, (int)N);
   a.bm = bn == 256 ? pick_bm(M, N, K, epi) : 256;

@@ -425,11 +425,11 @@ __global__ __launch_bounds__(XTHREADS, 1) void gemm_xl_nt_kernel(const XlArgs p)
 }
 
 // The PIPEs built per epilogue: 10 at 256-wide tiles only; the conv epilogues
-// (EPI >= XL_MOMENTS) have no two-buffer (PIPE 0) form.
+// (!is_linear_epi) have no two-buffer (PIPE 0) form.
 template <int EPI>
 void launch_nt8(const XlArgs& a, int bn, int pipe, int blocks, hipStream_t s) {
   const dim3 grid(blocks), block(XTHREADS);
-  constexpr bool kTwoBuf = EPI < XL_MOMENTS;
+  constexpr bool kTwoBuf = is_linear_epi(EPI);
   TORCH_CHECK((bn == 128 || bn == 256) && (pipe == 1 || (pipe == 10 && bn == 256) || (pipe == 0 && kTwoBuf)),
               "gemm_xl_nt_kernel: not built for epilogue ", EPI, " at bn ", bn, ", pipe ", pipe);
   if (pipe == 10) {
@@ -452,6 +452,7 @@ void xl::launch_xl_nt8(const XlArgs& a, int epi, int bn, int pipe, int blocks, h
     case XL_BIAS_GELU: launch_nt8<XL_BIAS_GELU>(a, bn, pipe, blocks, s); break;
     case XL_DGELU: launch_nt8<XL_DGELU>(a, bn, pipe, blocks, s); break;
     case XL_BIAS_RES: launch_nt8<XL_BIAS_RES>(a, bn, pipe, blocks, s); break;
+    case XL_BIAS_RES_SCALE: launch_nt8<XL_BIAS_RES_SCALE>(a, bn, pipe, blocks, s); break;
     case XL_MOMENTS: launch_nt8<XL_MOMENTS>(a, bn, pipe, blocks, s); break;
     case XL_ADD: launch_nt8<XL_ADD>(a, bn, pipe, blocks, s); break;
     case XL_BNBWD: launch_nt8<XL_BNBWD>(a, bn, pipe, blocks, s); break;

@@ -245,6 +245,7 @@ void xl::launch_xl_w4(const XlArgs& a, int epi, hipStream_t s) {
     case XL_BIAS_GELU: launch_w4_shape<XL_BIAS_GELU>(a, s); break;
     case XL_DGELU: launch_w4_shape<XL_DGELU>(a, s); break;
     case XL_BIAS_RES: launch_w4_shape<XL_BIAS_RES>(a, s); break;
+    case XL_BIAS_RES_SCALE: launch_w4_shape<XL_BIAS_RES_SCALE>(a, s); break;
     case XL_MOMENTS: launch_w4_shape<XL_MOMENTS>(a, s); break;
     case XL_ADD: launch_w4_shape<XL_ADD>(a, s); break;
     default: TORCH_CHECK(false, "gemm_xl_w4_kernel: not built for epilogue ", epi);

@@ -13,6 +13,10 @@
 //                the gradient at fc1's pre-activation: no GELU-backward pass)
 //   XL_BIAS_RES  C = bf16(bf16(acc + b[n]) + R)                    (proj / fc2
 //                forward + residual add)
+//   XL_BIAS_RES_SCALE  C = bf16(fma(bf16(acc + b[n]), s[m / rows_per_sample], R))
+//                (the same with a per-sample fp32 scale on the branch:
+//                stochastic depth.  s == 1 gives XL_BIAS_RES's bits, s == 0 the
+//                residual row)
 // Rounding points match the unfused torch sequence (addmm -> bf16 -> gelu).
 //
 // The plain structs and enums are in dmp::xl: they stand in the launchers'
@@ -39,7 +43,14 @@ enum XlEpi { XL_STORE = 0, XL_BIAS = 1, XL_BIAS_GELU = 2, XL_DGELU = 3, XL_BIAS_
              // XL_BNBWD with its operand set fixed at compile time (the runtime
              // flags cost the epilogue ~2x the VALU of the moments epilogue):
              // mask from y with x moments / mask from y, no x
-             XL_BNBWD_Y = 9, XL_BNBWD_YO = 10 };
+             XL_BNBWD_Y = 9, XL_BNBWD_YO = 10,
+             // XL_BIAS_RES with the branch scaled per sample (a linear epilogue
+             // numbered after the conv ones: the existing values, and with them
+             // every existing instantiation, stay as they were)
+             XL_BIAS_RES_SCALE = 11 };
+// the transformer-linear epilogues (two-buffer PIPE 0 form built, never on the
+// two-blocks-per-CU conv kernel); the rest are the conv epilogues
+__host__ __device__ constexpr bool is_linear_epi(int e) { return e < XL_MOMENTS || e == XL_BIAS_RES_SCALE; }
 __host__ __device__ constexpr bool is_bnbwd(int e) { return e == XL_BNBWD || e == XL_BNBWD_Y || e == XL_BNBWD_YO; }
 
 // Epilogues the 4-wave kernel takes.  The operand-heavy conv epilogues
@@ -89,6 +100,9 @@ struct XlArgs {
   // diagnostics (set_gemm_xl_trace): per block [entry, operands landed, main
   // loop done, epilogue done] in 10-ns ticks, HW_ID, XCC_ID; null = off
   unsigned long long* tdbg;
+  // XL_BIAS_RES_SCALE: fp32 scale per sample [M / rows_per_sample]; row m
+  // belongs to sample m / rows_per_sample (the T of a [B, T, D] activation)
+  const float* rscale; int rows_per_sample;
 };
 
 // One launcher per kernel file: the switch from the runtime choice to that
@@ -209,7 +223,7 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
   const int cvi = tid % CV, rr0 = tid / CV;
   const int col = n0 + cvi * 8;
   constexpr bool kBatch = is_bnbwd(EPI) || EPI == XL_ADD || EPI == XL_AFFINE || EPI == XL_BIAS_RES ||
-                          EPI == XL_DGELU;
+                          EPI == XL_DGELU || EPI == XL_BIAS_RES_SCALE;
   constexpr bool kL0 = kBatch;
   constexpr bool kL12 = is_bnbwd(EPI);
   constexpr bool kLx = EPI == XL_BNBWD || EPI == XL_BNBWD_Y, kLy = EPI == XL_BNBWD_Y || EPI == XL_BNBWD_YO;
@@ -241,6 +255,14 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
   const int64_t xstep = (int64_t)RPP * xld, ystep = (int64_t)RPP * yld;
   bf16x8 L0[NB][PB], L1[NB][PB], L2[NB][PB];
   unsigned rok[NB];  // bit i: row pass b PB + i has a residual row (compact map)
+  // XL_BIAS_RES_SCALE: the per-sample scale of each row pass, loaded with the
+  // batch.  row / rows_per_sample without a divide per pass: q = hi32(row * mg)
+  // with mg = floor((2^32 - 1) / d) is the quotient or one below it
+  // (row * mg / 2^32 > row / d - 1 for row < 2^31), one compare-and-add fixes it
+  constexpr bool kScale = EPI == XL_BIAS_RES_SCALE;
+  float S0[NB][PB];
+  const unsigned sdiv = kScale ? (unsigned)p.rows_per_sample : 1u;
+  const unsigned smg = 0xffffffffu / sdiv;
   auto issue = [&](const int b) {
     rok[b] = 0;
 #pragma unroll
@@ -259,6 +281,12 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
           rp = reinterpret_cast<const bf16x8*>(row_u < M ? rrow + pass * rstep : rbase + coll);
         }
         L0[b][i] = *rp;
+      }
+      if constexpr (kScale) {  // a row past M reads sample 0, as the residual reads row 0
+        const unsigned r = row_u < M ? (unsigned)row_u : 0u;
+        unsigned q = __umulhi(r, smg);
+        q += (r - q * sdiv >= sdiv) ? 1u : 0u;
+        S0[b][i] = p.rscale[q];
       }
       if constexpr (kL12) {
         if constexpr (kLx) L1[b][i] = *reinterpret_cast<const bf16x8*>(row_u < M ? xrow + pass * xstep : xbase + coll);
@@ -309,7 +337,7 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
     for (int j = 0; j < NI; ++j) {
       const int colj = min(n0 + wc * WTN + j * 16 + (lane >> 4) * 4, N - 4);  // N % 8 == 0
       f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, b4 = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (EPI == XL_BIAS || EPI == XL_BIAS_GELU || EPI == XL_BIAS_RES) {
+      if constexpr (EPI == XL_BIAS || EPI == XL_BIAS_GELU || EPI == XL_BIAS_RES || EPI == XL_BIAS_RES_SCALE) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) b4[e] = (float)p.bias[colj + e];  // a bias view may be 2-B aligned only
       }
@@ -349,7 +377,7 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
     const int col = n0 + wc * WTN + j * 16 + (lane & 15);
     bv[j] = 0.f;
     sv[j] = 1.f;
-    if constexpr (EPI == XL_BIAS || EPI == XL_BIAS_GELU || EPI == XL_BIAS_RES)
+    if constexpr (EPI == XL_BIAS || EPI == XL_BIAS_GELU || EPI == XL_BIAS_RES || EPI == XL_BIAS_RES_SCALE)
       bv[j] = col < N ? (float)p.bias[col] : 0.f;
     if constexpr (is_bnbwd(EPI))
       bv[j] = (col < N && p.ebias) ? p.ebias[col] : 0.f;
@@ -405,6 +433,13 @@ __device__ __forceinline__ void xl_epilogue(const XlArgs& p, ACC& acc, char* sme
         } else if constexpr (EPI == XL_ADD || EPI == XL_BIAS_RES) {
           f32x8 f = __builtin_convertvector(v, f32x8);
           f += __builtin_convertvector(L0[b][i], f32x8);
+          v = __builtin_convertvector(f, bf16x8);
+        } else if constexpr (EPI == XL_BIAS_RES_SCALE) {  // one fma, one rounding
+          f32x8 f = __builtin_convertvector(v, f32x8);
+          const f32x8 r = __builtin_convertvector(L0[b][i], f32x8);
+          const float sc = S0[b][i];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = fmaf(f[j], sc, r[j]);
           v = __builtin_convertvector(f, bf16x8);
         } else if constexpr (EPI == XL_AFFINE) {  // v = bf16(acc * s + t) (staged)
           f32x8 f = __builtin_convertvector(v, f32x8);

@@ -86,6 +86,8 @@ FEATURES = {
     "xl_conv": "256x256 GEMM for wide 1x1 convs (gemm_xl.hip gemm_xl_conv; kernels gemm_xl_w4.hip, gemm_xl_nt8.hip, gemm_xl_x2.hip)",
     "tn_xl": "ping-pong TN weight gradients of wide 1x1 convs and of the ViT linears",
     "xl_linear": "ViT MLP / attention projection on the fused-epilogue ping-pong GEMM -> hipBLASLt + GELU / add passes",
+    "fuse_drop_path": "stochastic depth's per-sample scale in the proj / fc2 GEMM store and the backward side pass "
+                      "(gemm_xl bias_res_scale, rowscale_bias_grad) -> the plain GEMM path + a scale and an add pass",
     "compact_shortcut": "stride-2 shortcut gradient kept compact (no zero-filled tensor)",
     "fuse_bn_bwd": "BN backward reductions in the consumer's data-gradient epilogue (BnBwdSlot)",
     "fuse_stem_pool": "stem BN apply + ReLU inside the max-pool (forward and backward)",

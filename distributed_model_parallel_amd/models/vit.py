@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.attention import self_attention_packed
+from ..ops.drop_path import sample_scales
 from ..ops.fused import GradSlot, grad_tap
 from ..ops.layernorm import LayerNorm
 from ..ops.linear import Linear, linear_gelu, linear_residual, mlp_residual
@@ -38,9 +39,11 @@ class MLP(nn.Module):
         x = F.dropout(x, self.dropout, self.training)
         return F.dropout(self.fc2(x), self.dropout, self.training)
 
-    def forward_residual(self, x: torch.Tensor, res: torch.Tensor) -> torch.Tensor:
-        """res + forward(x) with the GELU and residual add inside the GEMM epilogues."""
-        return mlp_residual(x, res, self.fc1, self.fc2, self.dropout, self.training)
+    def forward_residual(self, x: torch.Tensor, res: torch.Tensor,
+                         row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """res + forward(x) with the GELU and residual add inside the GEMM epilogues
+        (row_scale: res + row_scale[b] * forward(x), stochastic depth)."""
+        return mlp_residual(x, res, self.fc1, self.fc2, self.dropout, self.training, row_scale)
 
 
 class SelfAttention(nn.Module):
@@ -60,14 +63,19 @@ class SelfAttention(nn.Module):
     def _core(self, x: torch.Tensor) -> torch.Tensor:
         return self_attention_packed(self.qkv(x), self.heads, self.dropout if self.training else 0.0)
 
-    def forward_residual(self, x: torch.Tensor, res: torch.Tensor) -> torch.Tensor:
-        """res + forward(x): bias and residual added in the proj GEMM's store."""
-        return linear_residual(self._core(x), res, self.proj.weight, self.proj.bias)
+    def forward_residual(self, x: torch.Tensor, res: torch.Tensor,
+                         row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """res + forward(x): bias and residual added in the proj GEMM's store
+        (row_scale: res + row_scale[b] * forward(x), stochastic depth)."""
+        return linear_residual(self._core(x), res, self.proj.weight, self.proj.bias, row_scale)
 
 
 class EncoderBlock(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_dim: int, dropout: float = 0.0):
+    def __init__(self, dim: int, heads: int, mlp_dim: int, dropout: float = 0.0, drop_path: float = 0.0):
         super().__init__()
+        if not 0.0 <= drop_path < 1.0:
+            raise ValueError(f"drop_path must be in [0, 1), got {drop_path}")
+        self.drop_path = float(drop_path)  # stochastic depth rate of both branches (no parameter, no buffer)
         self.ln1 = LayerNorm(dim, eps=1e-6)
         self.attn = SelfAttention(dim, heads, dropout)
         self.ln2 = LayerNorm(dim, eps=1e-6)
@@ -78,20 +86,25 @@ class EncoderBlock(nn.Module):
         # branch's gradient of its input (ops/fused.py GradSlot) -- no add kernel.
         # The tap is created after the LN so its backward node runs first.
         train = self.training and torch.is_grad_enabled()
+        # stochastic depth: one draw per block, row 0 for the attention branch,
+        # row 1 for the MLP branch; rate 0 (and eval) makes no random call
+        dp = sample_scales(2, x.shape[0], self.drop_path, x.device) if train and self.drop_path > 0 else (None, None)
         s1 = GradSlot() if train else None
         h = self.ln1(x, s1)
-        x = self.attn.forward_residual(h, grad_tap(x, s1))
+        x = self.attn.forward_residual(h, grad_tap(x, s1), dp[0])
         s2 = GradSlot() if train else None
         h = self.ln2(x, s2)
-        return self.mlp.forward_residual(h, grad_tap(x, s2))
+        return self.mlp.forward_residual(h, grad_tap(x, s2), dp[1])
 
 
 class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch_size: int = 16, num_layers: int = 12,
                  num_heads: int = 12, hidden_dim: int = 768, mlp_dim: int = 3072,
-                 num_classes: int = 1000, dropout: float = 0.0):
+                 num_classes: int = 1000, dropout: float = 0.0, drop_path_rate: float = 0.0):
         super().__init__()
         assert image_size % patch_size == 0
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1), got {drop_path_rate}")
         self.patch_size = patch_size
         self.hidden_dim = hidden_dim
         # 16x16 / s16 conv as one MFMA GEMM over the patches (ops/patch_embed.py)
@@ -99,8 +112,11 @@ class VisionTransformer(nn.Module):
         n_tokens = (image_size // patch_size) ** 2 + 1
         self.cls_token = nn.Parameter(torch.zeros(1, 1, hidden_dim))
         self.pos_embedding = nn.Parameter(torch.empty(1, n_tokens, hidden_dim).normal_(std=0.02))
-        self.blocks = nn.Sequential(*[EncoderBlock(hidden_dim, num_heads, mlp_dim, dropout)
-                                      for _ in range(num_layers)])
+        # stochastic depth, the linear rule of DeiT / timm: block i of L drops
+        # its branches with probability drop_path_rate * i / (L - 1)
+        rates = [drop_path_rate * i / max(1, num_layers - 1) for i in range(num_layers)]
+        self.blocks = nn.Sequential(*[EncoderBlock(hidden_dim, num_heads, mlp_dim, dropout, rates[i])
+                                      for i in range(num_layers)])
         self.ln = LayerNorm(hidden_dim, eps=1e-6)
         self.head = nn.Linear(hidden_dim, num_classes)
         self._init()

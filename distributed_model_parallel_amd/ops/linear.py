@@ -22,6 +22,14 @@
   profiles/vit_xl_epilogues_r2.md).  ``DMP_DISABLE=xl_linear`` or
   ``set_xl_linear(False)`` selects hipBLASLt + the separate passes.
 
+* ``row_scale`` (stochastic depth, ``ops/drop_path.py``): a per-sample fp32
+  scale on the branch of ``mlp_residual`` / ``linear_residual``,
+  ``res + s[b] * branch``.  fc2 / proj apply it in the same store
+  (``gemm_xl`` mode ``bias_res_scale``: one FMA per element on the residual
+  row the epilogue already reads), and the backward forms the scaled gradient
+  and the bias gradient in one pass over ``dy`` (``rowscale_bias_grad``).
+  ``DMP_DISABLE=fuse_drop_path`` runs the same math in torch ops.
+
 CPU tensors, non-bf16 dtypes and widths that are not a multiple of 256 use
 the plain PyTorch ops (same math)."""
 from __future__ import annotations
@@ -33,7 +41,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _native
-from . import wgrad_stream
+from . import drop_path, wgrad_stream
 
 _STATS = {"native": 0, "torch": 0, "xl": 0, "tn_wgrad": 0, "xl_dgrad": 0, "xl_fwd": 0}
 _XL = not _native.disabled("xl_linear")
@@ -268,9 +276,82 @@ class _MLPResidualFn(torch.autograd.Function):
         return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2
 
 
+class _LinearResidualScaleFn(torch.autograd.Function):
+    """y = res + s[sample] * (x @ W^T + b): bias, per-sample scale and residual
+    in the GEMM's store.  The branch's gradient g = s * dy and the bias
+    gradient come from one pass over dy; the residual's gradient is dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, b, s):
+        C = _native.require("linear_residual (row_scale)")
+        x2, r2 = _rows(x), _rows(res)
+        ctx.rps = x2.shape[0] // s.numel()
+        y = C.gemm_xl(x2, w, "bias_res_scale", bias=b, residual=r2, row_scale=s, rows_per_sample=ctx.rps)
+        ctx.save_for_backward(x2, w, s)
+        ctx.xshape = x.shape
+        return y.view(res.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w, s = ctx.saved_tensors
+        C = _native.require("linear_residual backward (row_scale)")
+        g, db = C.rowscale_bias_grad(_rows(dy), s, ctx.rps, w.dtype)
+        dx = _dgrad(g, w).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        dw = _wgrad(g, x2, w) if ctx.needs_input_grad[2] else None
+        return dx, dy, dw, (db if ctx.needs_input_grad[3] else None), None
+
+
+class _MLPResidualScaleFn(torch.autograd.Function):
+    """_MLPResidualFn with fc2's output scaled per sample in its store; the
+    backward runs on g = s * dy (rowscale_bias_grad) where that one runs on dy."""
+
+    @staticmethod
+    def forward(ctx, x, res, w1, b1, w2, b2, s):
+        C = _native.require("mlp_residual (row_scale)")
+        x2, r2 = _rows(x), _rows(res)
+        ctx.rps = x2.shape[0] // s.numel()
+        h = torch.empty(x2.shape[0], w1.shape[0], dtype=x2.dtype, device=x2.device)
+        a = C.gemm_xl(x2, w1, "bias_gelu", bias=b1, aux=h)
+        y = C.gemm_xl(a, w2, "bias_res_scale", bias=b2, residual=r2, row_scale=s, rows_per_sample=ctx.rps)
+        ctx.save_for_backward(x2, w1, h, a, w2, s)
+        ctx.xshape = x.shape
+        return y.view(res.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w1, h, a, w2, s = ctx.saved_tensors
+        C = _native.require("mlp_residual backward (row_scale)")
+        g, db2 = C.rowscale_bias_grad(_rows(dy), s, ctx.rps, w2.dtype)
+        dw2 = _wgrad(g, a, w2)
+        from .wt_cache import transposed
+        dh, db1 = C.gemm_xl_dgelu_bgrad(g, transposed(w2), h)
+        db1 = db1.to(w1.dtype)
+        dw1 = _wgrad(dh, x2, w1)
+        dx = _dgrad(dh, w1)
+        return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2, None
+
+
+def _scale_ok(x: torch.Tensor, res: torch.Tensor, row_scale: torch.Tensor) -> bool:
+    """row_scale on the fused route: fp32 [B] on x's device for a [B, T, D] x."""
+    return (drop_path.fused() and x.dim() == 3 and res.shape == x.shape[:-1] + res.shape[-1:]
+            and row_scale.dtype == torch.float32 and row_scale.dim() == 1 and row_scale.shape[0] == x.shape[0]
+            and row_scale.device == x.device and row_scale.is_contiguous() and not row_scale.requires_grad)
+
+
+def _scaled(branch: torch.Tensor, row_scale: torch.Tensor) -> torch.Tensor:
+    return row_scale.view(-1, *([1] * (branch.dim() - 1))).to(branch.dtype) * branch
+
+
 def linear_residual(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
-                    bias: torch.Tensor) -> torch.Tensor:
-    """res + linear(x): one GEMM with the bias and residual in its epilogue."""
+                    bias: torch.Tensor, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """res + linear(x): one GEMM with the bias and residual in its epilogue.
+    ``row_scale`` (fp32 ``[B]`` for a ``[B, T, D]`` x): res + row_scale[b] * linear(x)."""
+    if row_scale is not None:
+        if (bias is not None and bias.dtype == torch.bfloat16 and _xl_ok(x, weight)
+                and res.dtype == torch.bfloat16 and _scale_ok(x, res, row_scale)):
+            _STATS["xl"] += 1
+            return _LinearResidualScaleFn.apply(x, res, weight, bias, row_scale)
+        return res + _scaled(linear(x, weight, bias), row_scale)
     if (bias is not None and bias.dtype == torch.bfloat16 and _xl_ok(x, weight)
             and res.dtype == torch.bfloat16 and res.shape[:-1] == x.shape[:-1]):
         _STATS["xl"] += 1
@@ -279,8 +360,19 @@ def linear_residual(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
 
 
 def mlp_residual(x: torch.Tensor, res: torch.Tensor, fc1: nn.Linear, fc2: nn.Linear,
-                 dropout: float = 0.0, training: bool = False) -> torch.Tensor:
-    """res + fc2(gelu(fc1(x))) (exact erf GELU, as ``nn.GELU()``)."""
+                 dropout: float = 0.0, training: bool = False,
+                 row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """res + fc2(gelu(fc1(x))) (exact erf GELU, as ``nn.GELU()``).
+    ``row_scale`` (fp32 ``[B]`` for a ``[B, T, D]`` x): res + row_scale[b] * fc2(...)."""
+    if row_scale is not None:
+        if ((dropout == 0.0 or not training) and fc1.bias is not None and fc2.bias is not None
+                and fc1.bias.dtype == torch.bfloat16 and fc2.bias.dtype == torch.bfloat16
+                and _xl_ok(x, fc1.weight, fc2.weight) and res.dtype == torch.bfloat16
+                and _scale_ok(x, res, row_scale)):
+            _STATS["xl"] += 1
+            return _MLPResidualScaleFn.apply(x, res, fc1.weight, fc1.bias, fc2.weight, fc2.bias, row_scale)
+        hdn = F.dropout(linear_gelu(x, fc1.weight, fc1.bias), dropout, training)
+        return res + _scaled(F.dropout(linear(hdn, fc2.weight, fc2.bias), dropout, training), row_scale)
     if ((dropout == 0.0 or not training) and fc1.bias is not None and fc2.bias is not None
             and fc1.bias.dtype == torch.bfloat16 and fc2.bias.dtype == torch.bfloat16
             and _xl_ok(x, fc1.weight, fc2.weight) and res.dtype == torch.bfloat16):

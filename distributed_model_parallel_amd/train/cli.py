@@ -69,6 +69,11 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
     if mixing and args.parallel == "pipe":
         parser.error("--mixup-alpha / --cutmix-alpha with --parallel pipe is not supported "
                      "(images enter at stage 0, labels are used at the last stage)")
+    if not 0.0 <= args.drop_path < 1.0:
+        parser.error("--drop-path must be in [0, 1)")
+    if args.drop_path > 0:
+        if not args.arch.startswith("vit"):
+            parser.error(f"--drop-path is for ViT archs only (vit_b_16, vit_tiny), not --arch {args.arch}")
     if args.image_size is not None:
         if not args.arch.startswith("vit"):
             parser.error(f"--image-size is for ViT archs only (vit_b_16, vit_tiny), not --arch {args.arch}")
@@ -147,6 +152,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "of the two with equal odds; acc1_train as for --mixup-alpha")
     p.add_argument("--mix-prob", default=None, type=float, metavar="P",
                    help="probability that a training batch is mixed (default 1.0; needs an alpha)")
+    p.add_argument("--drop-path", default=0.0, type=float, metavar="R",
+                   help="ViT archs only: stochastic depth, block i of L drops its residual branches per sample "
+                        "with probability R * i / (L - 1), in [0, 1) (0 = off; e.g. 0.1 for ViT-B from scratch)")
     p.add_argument("-r", "--resume", action="store_true")
     p.add_argument("--init-from", default="", metavar="CKPT",
                    help="initialise the model from CKPT's weights only (fine-tuning: no optimizer / scheduler / "
@@ -248,6 +256,8 @@ def run_data_parallel(args, env) -> None:
     dev = env.device
     dtype = parse_dtype(args.dtype)
     size_kw = {} if args.image_size is None else {"image_size": args.image_size}
+    if args.drop_path > 0:
+        size_kw["drop_path_rate"] = args.drop_path
     model = build_model(args.arch, num_classes=_num_classes(args), **size_kw)
     if args.init_from:
         from ..utils.checkpoint import load_weights
@@ -332,6 +342,8 @@ def run_data_parallel(args, env) -> None:
             best = va
             save_checkpoint(args.checkpoint, net, opt, sched, epoch, best)
         extra = _optimizer_log(args, opt)  # the epoch's last step; one read per epoch
+        if args.drop_path > 0:
+            extra["drop_path"] = args.drop_path  # the run's setting, in every epoch's JSONL record
         logger.log(epoch, loss_train=lm.avg, acc1_train=am.avg, loss_val=vl, acc1_val=va,
                    time_per_batch=step_s + data_s, time_load_perbatch=data_s,
                    images_per_sec=(args.batch_size * max(1, env.world_size if args.parallel == "ddp" else 1))

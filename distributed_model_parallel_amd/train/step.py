@@ -46,6 +46,7 @@ class StepConfig:
     clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
     trust_coefficient: float = 1e-3  # optimizer == "lars"
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
+    drop_path_rate: float = 0.0     # ViT only: stochastic depth, linear over the blocks (ops/drop_path.py)
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -120,6 +121,10 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
         kw["num_classes"] = cfg.num_classes
     if cfg.image_size and cfg.model.startswith("vit"):
         kw["image_size"] = cfg.image_size
+    if cfg.drop_path_rate:
+        if not cfg.model.startswith("vit"):
+            raise ValueError(f"drop_path_rate is for ViT models only, not {cfg.model}")
+        kw["drop_path_rate"] = cfg.drop_path_rate
     model = build_model(cfg.model, **kw)
     if cfg.checkpoint_segments > 1:
         from ..utils.checkpointing import enable_activation_checkpointing
