@@ -273,7 +273,8 @@ void adamw_prepare(const c10::optional<at::Tensor>& partials, at::Tensor& hyper,
 void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
                      const at::Tensor& grad, at::Tensor& param,
                      const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper, double lr,
-                     double beta1, double beta2, double eps, double weight_decay);
+                     double beta1, double beta2, double eps, double weight_decay,
+                     const c10::optional<at::Tensor>& ema, double ema_decay);
 int64_t adamw_grid_cap();  // most blocks adamw_flat_step launches (256 threads, 8 elements each)
 
 // ---- optim/fused_lars.hip ----
@@ -283,7 +284,7 @@ void lars_trust(const at::Tensor& partials, const at::Tensor& tensors, at::Tenso
                 double trust_coefficient, double weight_decay, double eps);
 void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
                     at::Tensor& param, const at::Tensor& items, const at::Tensor& coef, double lr,
-                    double momentum);
+                    double momentum, const c10::optional<at::Tensor>& ema, double ema_decay);
 int64_t lars_chunk_elems();   // most elements of one work item (one block of the norm / update kernels)
 int64_t lars_fold_threads();  // lanes that fold one tensor's partials in lars_trust
 
@@ -291,7 +292,7 @@ int64_t lars_fold_threads();  // lanes that fold one tensor's partials in lars_t
 void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mom,
                    const at::Tensor& grad, const at::Tensor& param, double lr, double wd,
                    double momentum, double dampening, bool nesterov, double grad_scale,
-                   bool first_step);
+                   bool first_step, const c10::optional<at::Tensor>& ema, double ema_decay);
 
 // ---- pool/maxpool.hip ----
 std::vector<at::Tensor> maxpool2d_forward(const at::Tensor& x, int64_t k, int64_t s, int64_t p);

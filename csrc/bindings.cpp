@@ -299,7 +299,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
 
   // ---- optimizer ----
-  m.def("sgd_flat_step", &dmp::sgd_flat_step,
+  m.def("sgd_flat_step", &dmp::sgd_flat_step, py::arg("master"), py::arg("mom"), py::arg("grad"),
+        py::arg("param"), py::arg("lr"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"),
+        py::arg("nesterov"), py::arg("grad_scale"), py::arg("first_step"), py::arg("ema") = py::none(),
+        py::arg("ema_decay") = 0.0,
         py::call_guard<py::gil_scoped_release>());
   m.def("flat_sumsq_partials", &dmp::flat_sumsq_partials, py::arg("grad"), py::arg("partials_row"),
         "partials_row[b] = block b's sum of squares of the flat gradient (fixed order, no atomics)",
@@ -311,6 +314,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_flat_step", &dmp::adamw_flat_step, py::arg("master"), py::arg("exp_avg"),
         py::arg("exp_avg_sq"), py::arg("grad"), py::arg("param"), py::arg("decay_mask"), py::arg("hyper"),
         py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0,
         py::call_guard<py::gil_scoped_release>());
   m.def("adamw_grid_cap", &dmp::adamw_grid_cap);
   m.def("lars_norm_partials", &dmp::lars_norm_partials, py::arg("master"), py::arg("grad"), py::arg("param"),
@@ -323,6 +327,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("lars_flat_step", &dmp::lars_flat_step, py::arg("master"), py::arg("mom"), py::arg("grad"),
         py::arg("param"), py::arg("items"), py::arg("coef"), py::arg("lr"), py::arg("momentum"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0,
         py::call_guard<py::gil_scoped_release>());
   m.def("lars_chunk_elems", &dmp::lars_chunk_elems);
   m.def("lars_fold_threads", &dmp::lars_fold_threads);

@@ -22,6 +22,7 @@
 #include <ATen/hip/HIPContext.h>
 #include "../api.h"
 #include "../common.h"
+#include "ema.h"
 
 namespace dmp {
 namespace {
@@ -90,12 +91,12 @@ __global__ __launch_bounds__(kThreads) void adamw_prepare_kernel(const float* __
   }
 }
 
-template <typename G, typename P, bool MASTER>
+template <typename G, typename P, bool MASTER, bool EMA>
 __global__ __launch_bounds__(kThreads) void adamw_flat_kernel(
     float* __restrict__ master, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
     const G* __restrict__ grad, P* __restrict__ param, const uint8_t* __restrict__ decay_mask,
     const float* __restrict__ hyper, int64_t n, float lr, float beta1, float beta2, float omb1,
-    float omb2, float eps, float decay) {
+    float omb2, float eps, float decay, float* __restrict__ ema, float omd) {
   // uniform per-step scalars: one load each, then SGPR-resident
   const float clip = hyper[kClip];
   const float step_size = lr / hyper[kBc1];
@@ -125,6 +126,13 @@ __global__ __launch_bounds__(kThreads) void adamw_flat_kernel(
     store8(exp_avg_sq + o, s);
     if constexpr (MASTER) store8(master + o, w);
     store8(param + o, w);
+    if constexpr (EMA) {  // e += (1 - decay) * (w - e) on the fp32 weights just formed
+      float e[8];
+      load8(ema + o, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = fmaf(omd, w[i] - e[i], e[i]);
+      store8(ema + o, e);
+    }
   }
 }
 
@@ -196,10 +204,13 @@ void adamw_prepare(const c10::optional<at::Tensor>& partials, at::Tensor& hyper,
 // exp_avg / exp_avg_sq: fp32 flat moments; grad / param: bf16 or fp32 flats
 // decay_mask: uint8 [numel / 8], one byte per 8-element vector (undefined:
 // decay everywhere); hyper: as written by adamw_prepare.
+// ema: fp32 flat average of the fp32 weights, ema += (1 - ema_decay) * (w - ema)
+// in the same pass (undefined: none).
 void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
                      const at::Tensor& grad, at::Tensor& param,
                      const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper, double lr,
-                     double beta1, double beta2, double eps, double weight_decay) {
+                     double beta1, double beta2, double eps, double weight_decay,
+                     const c10::optional<at::Tensor>& ema, double ema_decay) {
   const int64_t n = param.numel();
   check_flat(param, "param");
   check_flat(grad, "grad");
@@ -234,6 +245,7 @@ void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_av
                     decay_mask->get_device() == dev, "decay_mask must be uint8 [numel / 8]");
     dm = decay_mask->data_ptr<uint8_t>();
   }
+  float* ep = check_ema(ema, ema_decay, master, param);
   if (n == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   const int64_t nvec = n / 8;
@@ -241,21 +253,19 @@ void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_av
   // formed in double, rounded once: what torch's python-float hyper-parameters give
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   const float decay = (float)(1.0 - lr * weight_decay);
+  const float omd = (float)(1.0 - ema_decay);
   auto launch = [&](auto gtag, auto ptag) {
     using G = decltype(gtag);
     using P = decltype(ptag);
     const G* gp = reinterpret_cast<const G*>(grad.data_ptr());
     P* pp = reinterpret_cast<P*>(param.data_ptr());
-    if (has_master)
-      hipLaunchKernelGGL((adamw_flat_kernel<G, P, true>), dim3(blocks), dim3(kThreads), 0, stream, mp,
-                         exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), gp, pp, dm,
-                         hyper.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2, omb1, omb2,
-                         (float)eps, decay);
-    else
-      hipLaunchKernelGGL((adamw_flat_kernel<G, P, false>), dim3(blocks), dim3(kThreads), 0, stream, mp,
-                         exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), gp, pp, dm,
-                         hyper.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2, omb1, omb2,
-                         (float)eps, decay);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kThreads), 0, stream, mp, exp_avg.data_ptr<float>(),
+                         exp_avg_sq.data_ptr<float>(), gp, pp, dm, hyper.data_ptr<float>(), n, (float)lr,
+                         (float)beta1, (float)beta2, omb1, omb2, (float)eps, decay, ep, omd);
+    };
+    if (has_master) ep ? go(adamw_flat_kernel<G, P, true, true>) : go(adamw_flat_kernel<G, P, true, false>);
+    else ep ? go(adamw_flat_kernel<G, P, false, true>) : go(adamw_flat_kernel<G, P, false, false>);
   };
   if (gb && pb) launch(__bf16{}, __bf16{});
   else if (gb) launch(__bf16{}, float{});

@@ -30,6 +30,7 @@
 #include <ATen/hip/HIPContext.h>
 #include "../api.h"
 #include "../common.h"
+#include "ema.h"
 
 namespace dmp {
 namespace {
@@ -142,13 +143,14 @@ __global__ __launch_bounds__(kThreads) void lars_trust_kernel(const float* __res
 // Block b updates its item with its tensor's {trust, decay}: two uniform
 // loads, then the stream of sgd_flat_kernel (8 elements per lane; master,
 // momentum and gradient in; master, momentum and parameter out).
-template <typename G, typename P, bool MASTER>
+template <typename G, typename P, bool MASTER, bool EMA>
 __global__ __launch_bounds__(kThreads) void lars_flat_kernel(float* __restrict__ master,
                                                              float* __restrict__ mom,
                                                              const G* __restrict__ grad, P* __restrict__ param,
                                                              const int32_t* __restrict__ items,
                                                              const float* __restrict__ coef, int64_t nvec,
-                                                             int ntensors, float lr, float momentum) {
+                                                             int ntensors, float lr, float momentum,
+                                                             float* __restrict__ ema, float omd) {
   const Item it = load_item(items, nvec, ntensors);
   if (it.count == 0) return;
   const float trust = coef[(int64_t)it.tensor * kCoefCols + kTrust];
@@ -169,6 +171,13 @@ __global__ __launch_bounds__(kThreads) void lars_flat_kernel(float* __restrict__
     store8(mom + o, m);
     if constexpr (MASTER) store8(master + o, w);
     store8(param + o, w);
+    if constexpr (EMA) {  // e += (1 - decay) * (w - e) on the fp32 weights just formed
+      float e[8];
+      load8(ema + o, e);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) e[j] = fmaf(omd, w[j] - e[j], e[j]);
+      store8(ema + o, e);
+    }
   }
 }
 
@@ -252,9 +261,11 @@ void lars_trust(const at::Tensor& partials, const at::Tensor& tensors, at::Tenso
 
 // master: fp32 flat (or undefined when `param` is fp32 and is its own master)
 // mom: fp32 flat momentum; grad / param: bf16 or fp32 flats; items / coef: as above.
+// ema: fp32 flat average of the fp32 weights, ema += (1 - ema_decay) * (w - ema)
+// in the same pass (undefined: none); slot padding no work item covers is not touched.
 void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
                     at::Tensor& param, const at::Tensor& items, const at::Tensor& coef, double lr,
-                    double momentum) {
+                    double momentum, const c10::optional<at::Tensor>& ema, double ema_decay) {
   check_flat(param, "param");
   check_flat(grad, "grad");
   check_flat(mom, "mom");
@@ -272,6 +283,8 @@ void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, co
   float* mp = has_master ? master->data_ptr<float>() : nullptr;
   check_plan(items, "items", at::kInt, kItemCols, dev);
   check_plan(coef, "coef", at::kFloat, kCoefCols, dev);
+  float* ep = check_ema(ema, ema_decay, master, param);
+  const float omd = (float)(1.0 - ema_decay);  // formed in double, rounded once
   const int64_t nitems = items.size(0);
   if (nitems == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
@@ -280,14 +293,13 @@ void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, co
     using P = decltype(ptag);
     const G* gp = reinterpret_cast<const G*>(grad.data_ptr());
     P* pp = reinterpret_cast<P*>(param.data_ptr());
-    if (has_master)
-      hipLaunchKernelGGL((lars_flat_kernel<G, P, true>), dim3((unsigned)nitems), dim3(kThreads), 0, stream, mp,
-                         mom.data_ptr<float>(), gp, pp, items.data_ptr<int32_t>(), coef.data_ptr<float>(), n / 8,
-                         (int)coef.size(0), (float)lr, (float)momentum);
-    else
-      hipLaunchKernelGGL((lars_flat_kernel<G, P, false>), dim3((unsigned)nitems), dim3(kThreads), 0, stream, mp,
-                         mom.data_ptr<float>(), gp, pp, items.data_ptr<int32_t>(), coef.data_ptr<float>(), n / 8,
-                         (int)coef.size(0), (float)lr, (float)momentum);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)nitems), dim3(kThreads), 0, stream, mp, mom.data_ptr<float>(), gp,
+                         pp, items.data_ptr<int32_t>(), coef.data_ptr<float>(), n / 8, (int)coef.size(0), (float)lr,
+                         (float)momentum, ep, omd);
+    };
+    if (has_master) ep ? go(lars_flat_kernel<G, P, true, true>) : go(lars_flat_kernel<G, P, true, false>);
+    else ep ? go(lars_flat_kernel<G, P, false, true>) : go(lars_flat_kernel<G, P, false, false>);
   };
   if (gb && pb) launch(__bf16{}, __bf16{});
   else if (gb) launch(__bf16{}, float{});

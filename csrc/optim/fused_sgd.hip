@@ -14,15 +14,16 @@
 #include <ATen/hip/HIPContext.h>
 #include "../api.h"
 #include "../common.h"
+#include "ema.h"
 
 namespace dmp {
 namespace {
 
-template <typename G, typename P, bool MASTER>
+template <typename G, typename P, bool MASTER, bool EMA>
 __global__ __launch_bounds__(256) void sgd_flat_kernel(
     float* __restrict__ master, float* __restrict__ mom, const G* __restrict__ grad,
     P* __restrict__ param, int64_t n, float lr, float wd, float momentum, float dampening,
-    int nesterov, float grad_scale, int first_step) {
+    int nesterov, float grad_scale, int first_step, float* __restrict__ ema, float omd) {
   // 8 elements per lane per iteration: bf16 grads/params = 16 B, fp32 = 2 x 16 B.
   const int64_t nvec = n / 8;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -79,6 +80,13 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(
       Vec16<float>::store(reinterpret_cast<float*>(param) + o, a);
       Vec16<float>::store(reinterpret_cast<float*>(param) + o + 4, b);
     }
+    if constexpr (EMA) {  // e += (1 - decay) * (w - e) on the fp32 weights just formed
+      float e[8];
+      load8(ema + o, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = fmaf(omd, w[i] - e[i], e[i]);
+      store8(ema + o, e);
+    }
   }
 }
 
@@ -88,10 +96,12 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(
 // mom:    fp32 flat momentum buffer (ignored when momentum == 0)
 // grad:   flat gradient (bf16 or fp32), param: flat parameters (bf16 or fp32)
 // numel must be a multiple of 8 (bucket layouts are padded to 16 B).
+// ema:    fp32 flat average of the fp32 weights, ema += (1 - ema_decay) * (w - ema)
+//         in the same pass (undefined: none)
 void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mom,
                    const at::Tensor& grad, const at::Tensor& param, double lr, double wd,
                    double momentum, double dampening, bool nesterov, double grad_scale,
-                   bool first_step) {
+                   bool first_step, const c10::optional<at::Tensor>& ema, double ema_decay) {
   const int64_t n = param.numel();
   TORCH_CHECK(grad.numel() == n, "grad/param size mismatch");
   TORCH_CHECK(n % 8 == 0, "flat buffers must be padded to a multiple of 8 elements");
@@ -99,6 +109,7 @@ void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mo
   const bool has_master = master.has_value() && master->defined();
   TORCH_CHECK(has_master || param.scalar_type() == at::kFloat,
               "bf16 parameters need an fp32 master buffer");
+  float* ep = check_ema(ema, ema_decay, master, param);
   if (n == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   const int64_t nvec = n / 8;
@@ -106,19 +117,19 @@ void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mo
   const int64_t blocks = std::min<int64_t>((nvec + threads - 1) / threads, 256 * 8);
   float* mp = has_master ? master->data_ptr<float>() : nullptr;
   float* mo = momentum != 0.0 ? mom.data_ptr<float>() : nullptr;
+  const float omd = (float)(1.0 - ema_decay);  // formed in double, rounded once
   auto launch = [&](auto gtag, auto ptag) {
     using G = decltype(gtag);
     using P = decltype(ptag);
     const G* gp = reinterpret_cast<const G*>(grad.data_ptr());
     P* pp = reinterpret_cast<P*>(param.data_ptr());
-    if (has_master)
-      hipLaunchKernelGGL((sgd_flat_kernel<G, P, true>), dim3(blocks), dim3(threads), 0, stream, mp,
-                         mo, gp, pp, n, (float)lr, (float)wd, (float)momentum, (float)dampening,
-                         (int)nesterov, (float)grad_scale, (int)first_step);
-    else
-      hipLaunchKernelGGL((sgd_flat_kernel<G, P, false>), dim3(blocks), dim3(threads), 0, stream, mp,
-                         mo, gp, pp, n, (float)lr, (float)wd, (float)momentum, (float)dampening,
-                         (int)nesterov, (float)grad_scale, (int)first_step);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, mp, mo, gp, pp, n, (float)lr,
+                         (float)wd, (float)momentum, (float)dampening, (int)nesterov, (float)grad_scale,
+                         (int)first_step, ep, omd);
+    };
+    if (has_master) ep ? go(sgd_flat_kernel<G, P, true, true>) : go(sgd_flat_kernel<G, P, true, false>);
+    else ep ? go(sgd_flat_kernel<G, P, false, true>) : go(sgd_flat_kernel<G, P, false, false>);
   };
   const bool gb = grad.scalar_type() == at::kBFloat16, pb = param.scalar_type() == at::kBFloat16;
   if (gb && pb) launch(__bf16{}, __bf16{});

@@ -101,6 +101,8 @@ FEATURES = {
                        "-> the apply pass + one weight gradient",
     "fuse_stem_pool_wgrad": "stem pool / ReLU backward formed inside the stem weight-gradient kernel "
                             "(stem_halo.hip stem_halo_wgrad_pool) -> maxpool2d_bn_backward + two stem_halo_wgrad",
+    "fuse_ema": "weight EMA updated inside the flat optimizers' step kernels (ops/optim.py ema_decay) "
+                "-> the step kernel + a lerp_ pass over the masters",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",
 }

@@ -22,9 +22,19 @@ Reference parity: SGD(lr, momentum 0.9, weight_decay 1e-4) at
 with decoupled decay off for biases / norm weights and global-norm clipping is
 what every ViT recipe trains with; LARS (per-tensor trust ratios from a
 segmented norm over the flats) is what large-batch ResNet recipes train with.
+
+Every class can keep an exponential moving average of the weights
+(``ema_decay``): an fp32 flat per group, averaged over the fp32 MASTERS (a bf16
+average at decay 0.9999 never moves: the increment is far below one bf16 ulp)
+and updated inside the step kernel, which holds every new master value in
+registers when it stores it (+8 B per element, no launch).
+``DMP_DISABLE=fuse_ema`` (or ``set_fused_ema(False)``) runs the step kernel
+without it and a ``lerp_`` pass after it.
 """
 from __future__ import annotations
 
+import contextlib
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -32,6 +42,17 @@ import torch
 from .. import _native
 from . import wgrad_stream, wt_cache
 
+_FUSED_EMA = not _native.disabled("fuse_ema")
+
+
+def set_fused_ema(on: bool) -> None:
+    """Weight EMA inside the step kernels (True) or as a ``lerp_`` pass after them."""
+    global _FUSED_EMA
+    _FUSED_EMA = bool(on)
+
+
+def fused_ema() -> bool:
+    return _FUSED_EMA
 
 
 class ForeignOptimizerState(ValueError):
@@ -61,12 +82,42 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _name(self) -> str:
         return type(self).__name__
 
+    def _init_ema(self, ema_decay: Optional[float], ema_warmup: bool) -> None:
+        d = float(ema_decay or 0.0)
+        if not 0.0 <= d < 1.0:
+            raise ValueError("%s: ema_decay must be in [0, 1), got %r" % (self._name(), ema_decay))
+        self.ema_decay = d
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_updates = 0      # host counter: the warm-up's k
+        self._ema_now = 0.0        # decay of the update in flight (a host scalar, like lr)
+        self._ema_swapped = False  # inside ema_weights()
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self.ema_decay > 0.0
+
     def _alloc_state(self, st: dict) -> None:
         pflat = st["param"]
         if pflat.dtype != torch.float32 and self.master_weights:
             st["master"] = pflat.float()
         for k in self.STATE_KEYS:
             st[k] = torch.zeros(pflat.numel(), dtype=torch.float32, device=pflat.device)
+        if self.ema_enabled:  # starts at the weights the optimizer was built on; slot padding stays 0
+            st["ema"] = st.get("master", pflat).detach().to(torch.float32, copy=True)
+
+    def ema_decay_of_update(self, k: int) -> float:
+        """Decay of EMA update number ``k`` (0-based): ``ema_decay``, or with
+        ``ema_warmup`` ``min(ema_decay, (1 + k) / (10 + k))``."""
+        if self.ema_warmup:
+            return min(self.ema_decay, (1.0 + k) / (10.0 + k))
+        return self.ema_decay
+
+    def _ema_args(self, st: dict):
+        """(ema, ema_decay) for the group's step kernel: (None, 0.0) where the
+        EMA is off or follows the kernel as a pass of its own."""
+        if self.ema_enabled and _FUSED_EMA and st["param"].is_cuda:
+            return st["ema"], self._ema_now
+        return None, 0.0
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -74,11 +125,25 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.ema_enabled:
+            if self._ema_swapped:
+                raise RuntimeError("%s.step() inside ema_weights(): the working weights are the EMA's"
+                                   % self._name())
+            if self.ema_warmup and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise ValueError("%s: ema_warmup cannot be captured into a graph: the decay is a host scalar, "
+                                 "a replay would keep the warm-up value of the captured step for ever; "
+                                 "use a constant ema_decay" % self._name())
+            self._ema_now = self.ema_decay_of_update(self._ema_updates)
         groups = self._current_groups()
         if groups and groups[0]["param"].is_cuda:
             wgrad_stream.join(groups[0]["param"].device)  # gradients from the side stream
         self._update(groups)
         self._steps += 1
+        if self.ema_enabled:
+            for st in groups:
+                if self._ema_args(st)[0] is None:  # CPU, or the unfused route on the GPU
+                    _ema_reference(st["ema"], st.get("master", st["param"]), 1.0 - self._ema_now)
+            self._ema_updates += 1
         # the updated weights' W^T, one launch (ops/wt_cache.py)
         wt_cache.after_optimizer_step(p for grp in self.param_groups for p in grp["params"])
         return loss
@@ -93,6 +158,70 @@ class _FlatOptimizer(torch.optim.Optimizer):
         for st in self._state_groups():
             if "master" in st:
                 st["master"].copy_(st["param"])
+        self._seed_ema()  # an average of the replaced weights means nothing
+
+    @torch.no_grad()
+    def _seed_ema(self) -> None:
+        for st in self._state_groups():
+            if "ema" in st:
+                st["ema"].copy_(st.get("master", st["param"]))
+        self._ema_updates = 0
+
+    def ema_tensors(self) -> List[torch.Tensor]:
+        """Per parameter (``param_groups`` order) an fp32 view of its EMA slot, shaped like the parameter."""
+        if not self.ema_enabled:
+            raise RuntimeError("%s was built without ema_decay" % self._name())
+        views = {}
+        for gi, st in enumerate(self._current_groups()):
+            for p, off in self._slots(gi):
+                views[id(p)] = st["ema"].as_strided(p.shape, p.stride(), off)
+        return [views[id(p)] for grp in self.param_groups for p in grp["params"]]
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model's working weights are the EMA
+        (``ema.to(dtype)``); afterwards they are the live ones again, bit for
+        bit.  The EMA and its update count are unchanged by a round trip.
+        Buffers (BatchNorm running statistics) are not averaged: the live ones
+        are used.  ``step()`` must not be called inside, and ``state_dict()`` /
+        ``ema_tensors()`` not be read there: the EMA flat of an fp32 group
+        without a master holds the live weights meanwhile."""
+        if not self.ema_enabled:
+            raise RuntimeError("%s was built without ema_decay" % self._name())
+        if self._ema_swapped:
+            raise RuntimeError("%s.ema_weights() is already entered" % self._name())
+        groups = self._current_groups()
+        params = [p for grp in self.param_groups for p in grp["params"]]
+
+        def swap(st):  # fp32 parameters that are their own master: exchange contents
+            tmp = st["param"].clone()
+            st["param"].copy_(st["ema"])
+            st["ema"].copy_(tmp)
+
+        for st in groups:
+            if "master" not in st and st["param"].dtype != torch.float32:
+                raise RuntimeError("%s.ema_weights(): %s parameters without an fp32 master"
+                                   % (self._name(), st["param"].dtype))
+        with torch.no_grad():
+            for st in groups:
+                if "master" in st:
+                    st["param"].copy_(st["ema"])  # rounds as .to(dtype)
+                else:
+                    swap(st)
+            # writes through the flat do not bump p._version: cached W^T / casts are re-formed here
+            wt_cache.after_optimizer_step(params)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for st in groups:
+                    if "master" in st:
+                        st["param"].copy_(st["master"])  # param == dtype(master), the step's invariant
+                    else:
+                        swap(st)
+                wt_cache.after_optimizer_step(params)
+            self._ema_swapped = False
 
     def _step_count(self) -> int:
         return self._steps
@@ -101,13 +230,15 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._steps = int(n)
 
     def _saved_keys(self) -> Tuple[str, ...]:
-        return self.STATE_KEYS + ("master",)
+        return self.STATE_KEYS + (("master", "ema") if self.ema_enabled else ("master",))
 
     def _state_header(self) -> dict:
         sd = {"steps": self._step_count(),
               "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
         if self.KIND != "sgd":  # SGD states keep the format older checkpoints have
             sd["kind"] = self.KIND
+        if self.ema_enabled:
+            sd["ema_updates"] = self._ema_updates
         return sd
 
     def _check_kind(self, sd) -> None:
@@ -120,6 +251,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._set_step_count(sd["steps"])
         for g, sg in zip(self.param_groups, sd["param_groups"]):
             g.update(sg)
+        self._ema_updates = int(sd.get("ema_updates", 0)) if self.ema_enabled else 0
+
+    def _ema_after_load(self, sd) -> None:
+        """A state written without EMA, loaded with EMA on: the average starts at the restored weights."""
+        if self.ema_enabled and not all("ema" in sst for sst in sd["flat_state"]):
+            self._seed_ema()
+            warnings.warn("%s.load_state_dict: the state has no weight EMA; it starts from the restored "
+                          "weights" % self._name())
 
     @torch.no_grad()
     def _params_follow_masters(self) -> None:
@@ -134,7 +273,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
 class _DDPLayout:
     """Flats borrowed from ``DistributedDataParallel(flat_parameters=True)``."""
 
-    def _init_layout(self, ddp, master_weights: bool) -> None:
+    def _init_layout(self, ddp, master_weights: bool, ema_decay=None, ema_warmup=False) -> None:
+        self._init_ema(ema_decay, ema_warmup)
         self.ddp = ddp
         self.master_weights = master_weights
         self._version = -1
@@ -214,6 +354,7 @@ class _DDPLayout:
                              % (self._name(), len(old_layout), len(self.ddp._params)))
         self._remap(saved, self._flat_state, old_layout, self.ddp.param_layout())
         self._params_follow_masters()
+        self._ema_after_load(sd)
 
 
 class _ListLayout:
@@ -223,7 +364,8 @@ class _ListLayout:
     pre-set to views of a flat gradient buffer, so autograd accumulates in
     place and the update is one launch per group."""
 
-    def _init_layout(self, params, master_weights: bool) -> None:
+    def _init_layout(self, params, master_weights: bool, ema_decay=None, ema_warmup=False) -> None:
+        self._init_ema(ema_decay, ema_warmup)
         self.master_weights = master_weights
         self._steps = 0
         self._groups = []
@@ -310,6 +452,7 @@ class _ListLayout:
                     if k in st:
                         st[k].copy_(v)
         self._params_follow_masters()
+        self._ema_after_load(sd)
 
 
 # --------------------------------------------------------------------------- #
@@ -334,7 +477,8 @@ class _SGDRule:
             if pflat.is_cuda:
                 _native.require(self._name()).sgd_flat_step(
                     master, st["momentum"], gflat, pflat, float(g["lr"]), float(g["weight_decay"]),
-                    float(g["momentum"]), float(g["dampening"]), bool(g["nesterov"]), 1.0, first)
+                    float(g["momentum"]), float(g["dampening"]), bool(g["nesterov"]), 1.0, first,
+                    *self._ema_args(st))
             else:
                 _sgd_reference(master, st["momentum"], gflat, pflat, g, first)
 
@@ -450,7 +594,8 @@ class _AdamWRule:
             if pflat.is_cuda:
                 _native.require(self._name()).adamw_flat_step(
                     st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, mask, hyper,
-                    float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]))
+                    float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
+                    *self._ema_args(st))
             else:
                 _adamw_reference(st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat,
                                  mask, hyper, g)
@@ -570,7 +715,7 @@ class _LARSRule:
                 C.lars_trust(plan["partials"], plan["tensors"], plan["coef"], float(g["trust_coefficient"]),
                              float(g["weight_decay"]), float(g["eps"]))
                 C.lars_flat_step(master, st["momentum"], st["grad"], pflat, plan["items"], plan["coef"],
-                                 float(g["lr"]), float(g["momentum"]))
+                                 float(g["lr"]), float(g["momentum"]), *self._ema_args(st))
             else:
                 _lars_reference(master, st["momentum"], st["grad"], pflat, plan["spans"], plan["coef"], g)
         self._stepped = True
@@ -602,10 +747,11 @@ class _LARSRule:
 # --------------------------------------------------------------------------- #
 class FlatSGD(_SGDRule, _DDPLayout, _FlatOptimizer):
     def __init__(self, ddp, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
+                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._sgd_defaults(lr, momentum, dampening, weight_decay, nesterov)
         super().__init__(list(ddp._params), defaults)
-        self._init_layout(ddp, master_weights)
+        self._init_layout(ddp, master_weights, ema_decay, ema_warmup)
 
 
 class MasterSGD(_SGDRule, _ListLayout, _FlatOptimizer):
@@ -621,11 +767,12 @@ class MasterSGD(_SGDRule, _ListLayout, _FlatOptimizer):
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True):
+                 weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._sgd_defaults(lr, momentum, dampening, weight_decay, nesterov)
         params = [p for p in params if p.requires_grad]
         super().__init__(params, defaults)
-        self._init_layout(params, master_weights)
+        self._init_layout(params, master_weights, ema_decay, ema_warmup)
 
 
 class FlatAdamW(_AdamWRule, _DDPLayout, _FlatOptimizer):
@@ -640,11 +787,12 @@ class FlatAdamW(_AdamWRule, _DDPLayout, _FlatOptimizer):
 
     def __init__(self, ddp, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  max_grad_norm: Optional[float] = None, no_decay_1d: bool = True,
-                 master_weights: bool = True, amsgrad: bool = False, maximize: bool = False):
+                 master_weights: bool = True, amsgrad: bool = False, maximize: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
                                         amsgrad, maximize)
         super().__init__(list(ddp._params), defaults)
-        self._init_layout(ddp, master_weights)
+        self._init_layout(ddp, master_weights, ema_decay, ema_warmup)
 
 
 class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
@@ -653,7 +801,7 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
     def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None,
                  no_decay_1d: bool = True, master_weights: bool = True, amsgrad: bool = False,
-                 maximize: bool = False):
+                 maximize: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
                                         amsgrad, maximize)
         params = list(params)
@@ -664,7 +812,7 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
             params = list(params[0]["params"])
         params = [p for p in params if p.requires_grad]
         super().__init__(params, defaults)
-        self._init_layout(params, master_weights)
+        self._init_layout(params, master_weights, ema_decay, ema_warmup)
         self._clip_devices(self._groups)
 
 
@@ -676,10 +824,11 @@ class FlatLARS(_LARSRule, _DDPLayout, _FlatOptimizer):
 
     def __init__(self, ddp, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
                  trust_coefficient: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True,
-                 master_weights: bool = True):
+                 master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._lars_defaults(lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d)
         super().__init__(list(ddp._params), defaults)
-        self._init_layout(ddp, master_weights)
+        self._init_layout(ddp, master_weights, ema_decay, ema_warmup)
 
 
 class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
@@ -687,7 +836,8 @@ class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
 
     def __init__(self, params, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
                  trust_coefficient: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True,
-                 master_weights: bool = True):
+                 master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._lars_defaults(lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d)
         params = list(params)
         if params and isinstance(params[0], dict):
@@ -697,31 +847,41 @@ class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
             params = list(params[0]["params"])
         params = [p for p in params if p.requires_grad]
         super().__init__(params, defaults)
-        self._init_layout(params, master_weights)
+        self._init_layout(params, master_weights, ema_decay, ema_warmup)
 
 
 def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 0.9,
                     weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                    clip_grad_norm: float = 0.0, trust_coefficient: float = 1e-3):
+                    clip_grad_norm: float = 0.0, trust_coefficient: float = 1e-3,
+                    ema_decay: Optional[float] = None, ema_warmup: bool = False):
     """The trainer's optimizer: ``kind`` sgd | adamw | lars; ``flat`` picks the
-    DDP-flat class (``target`` is the DDP wrapper) over the parameter-list one."""
+    DDP-flat class (``target`` is the DDP wrapper) over the parameter-list one.
+    ``ema_decay`` (``None`` / 0 = off) keeps a weight EMA in the optimizer."""
     if kind in ("sgd", "lars") and clip_grad_norm:
         raise ValueError("gradient clipping needs optimizer='adamw'")
+    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if kind == "sgd":
-        return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                                **ema)
     if kind == "adamw":
         return (FlatAdamW if flat else MasterAdamW)(target, lr=lr, betas=betas, eps=eps,
                                                     weight_decay=weight_decay,
-                                                    max_grad_norm=clip_grad_norm or None)
+                                                    max_grad_norm=clip_grad_norm or None, **ema)
     if kind == "lars":
         return (FlatLARS if flat else MasterLARS)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
-                                                  trust_coefficient=trust_coefficient, eps=eps)
+                                                  trust_coefficient=trust_coefficient, eps=eps, **ema)
     raise ValueError(f"unknown optimizer {kind!r} (sgd | adamw | lars)")
 
 
 # --------------------------------------------------------------------------- #
 # PyTorch implementations of the kernels (CPU path / test oracle)
 # --------------------------------------------------------------------------- #
+def _ema_reference(ema: torch.Tensor, w: torch.Tensor, omd: float) -> None:
+    """``ema += omd * (w - ema)`` in fp32: the CPU path, and the unfused GPU
+    route (one more read of the weights and one more launch than the kernels')."""
+    ema.lerp_(w if w.dtype == torch.float32 else w.float(), float(omd))
+
+
 def _sgd_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: torch.Tensor,
                    param: torch.Tensor, g: dict, first: bool) -> None:
     """PyTorch implementation of the flat kernel (CPU path / test oracle)."""

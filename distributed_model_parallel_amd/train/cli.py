@@ -82,6 +82,15 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
             parser.error(f"--image-size must be a positive multiple of the patch size {patch} of {args.arch}")
         if args.parallel == "pipe":
             parser.error("--image-size with --parallel pipe is not supported")
+    if not 0.0 <= args.model_ema_decay < 1.0:
+        parser.error("--model-ema-decay must be in [0, 1)")
+    if args.model_ema_warmup and not args.model_ema_decay:
+        parser.error("--model-ema-warmup needs --model-ema-decay")
+    if args.model_ema_decay and args.parallel == "pipe":
+        parser.error("--model-ema-decay with --parallel pipe is not supported "
+                     "(per-stage optimizers and eval_step do not carry the average)")
+    if args.init_from_ema and not args.init_from:
+        parser.error("--init-from-ema needs --init-from")
     if args.init_from:
         if not os.path.exists(args.init_from):
             parser.error(f"--init-from: no such file {args.init_from}")
@@ -101,7 +110,9 @@ def _optimizer(args, target, flat: bool):
     trust = TRUST_COEFFICIENT if args.trust_coefficient is None else args.trust_coefficient
     return build_optimizer(args.optimizer, target, flat, lr=args.lr, momentum=args.momentum,
                            weight_decay=args.weight_decay, betas=args.betas, eps=args.eps,
-                           clip_grad_norm=args.clip_grad_norm, trust_coefficient=trust)
+                           clip_grad_norm=args.clip_grad_norm, trust_coefficient=trust,
+                           ema_decay=getattr(args, "model_ema_decay", 0.0) or None,
+                           ema_warmup=getattr(args, "model_ema_warmup", False))
 
 
 def _optimizer_log(args, opt) -> dict:
@@ -155,11 +166,22 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--drop-path", default=0.0, type=float, metavar="R",
                    help="ViT archs only: stochastic depth, block i of L drops its residual branches per sample "
                         "with probability R * i / (L - 1), in [0, 1) (0 = off; e.g. 0.1 for ViT-B from scratch)")
+    p.add_argument("--model-ema-decay", default=0.0, type=float, metavar="D",
+                   help="keep an exponential moving average of the fp32 master weights inside the optimizer's "
+                        "step kernels, decay D in [0, 1) (0 = off; e.g. 0.9999); every epoch also evaluates it "
+                        "(loss_val_ema / acc1_val_ema) and checkpoints carry it as net_ema.  BatchNorm running "
+                        "statistics are not averaged: the EMA evaluation uses the live buffers.  Checkpoint "
+                        "selection stays on the live accuracy; not with --parallel pipe")
+    p.add_argument("--model-ema-warmup", action="store_true",
+                   help="--model-ema-decay: update k uses min(D, (1 + k) / (10 + k)), so the average follows "
+                        "the weights early on")
     p.add_argument("-r", "--resume", action="store_true")
     p.add_argument("--init-from", default="", metavar="CKPT",
                    help="initialise the model from CKPT's weights only (fine-tuning: no optimizer / scheduler / "
                         "RNG state; a ViT position embedding of another resolution is resized bicubically); "
                         "not together with --resume from an existing checkpoint")
+    p.add_argument("--init-from-ema", action="store_true",
+                   help="--init-from: take CKPT's averaged weights (net_ema, written by a --model-ema-decay run)")
     p.add_argument("--image-size", default=None, type=int, metavar="N",
                    help="ViT archs only: train at N x N pixels (model, ImageNet transforms and synthetic data)")
     p.add_argument("--arch", default="mobilenetv2")
@@ -261,7 +283,7 @@ def run_data_parallel(args, env) -> None:
     model = build_model(args.arch, num_classes=_num_classes(args), **size_kw)
     if args.init_from:
         from ..utils.checkpoint import load_weights
-        load_weights(args.init_from, model)  # before the cast and the optimizer: masters start from these
+        load_weights(args.init_from, model, ema=args.init_from_ema)  # before the cast and the optimizer: masters start from these
     if args.checkpoint_segments > 1:
         from ..utils.checkpointing import enable_activation_checkpointing
         enable_activation_checkpointing(model, args.checkpoint_segments)
@@ -337,11 +359,18 @@ def run_data_parallel(args, env) -> None:
         tm = timer.summary()  # device time of the step (HIP events), host time of the data wait
         step_s, data_s = tm.get("step", 0.0) / 1e3, tm.get("data_host", 0.0) / 1e3
         vl, va = evaluate(net, val_loader, to_dev, args)
+        ema_log, ck_extra = {}, None
+        if args.model_ema_decay:  # the averaged weights on the live buffers (BN statistics are not averaged)
+            with opt.ema_weights():
+                vle, vae = evaluate(net, val_loader, to_dev, args)
+            ema_log = {"loss_val_ema": vle, "acc1_val_ema": vae, "ema_decay": args.model_ema_decay}
+            ck_extra = {"acc_ema": float(vae)}
         sched.step()
-        if env.is_main and va > best:
+        if env.is_main and va > best:  # selection stays on the live accuracy
             best = va
-            save_checkpoint(args.checkpoint, net, opt, sched, epoch, best)
+            save_checkpoint(args.checkpoint, net, opt, sched, epoch, best, extra=ck_extra)
         extra = _optimizer_log(args, opt)  # the epoch's last step; one read per epoch
+        extra.update(ema_log)
         if args.drop_path > 0:
             extra["drop_path"] = args.drop_path  # the run's setting, in every epoch's JSONL record
         logger.log(epoch, loss_train=lm.avg, acc1_train=am.avg, loss_val=vl, acc1_val=va,

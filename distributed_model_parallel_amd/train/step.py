@@ -47,6 +47,7 @@ class StepConfig:
     trust_coefficient: float = 1e-3  # optimizer == "lars"
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
     drop_path_rate: float = 0.0     # ViT only: stochastic depth, linear over the blocks (ops/drop_path.py)
+    ema_decay: float = 0.0          # weight EMA inside the optimizer's step kernels (ops/optim.py); 0 = off
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -86,7 +87,8 @@ def synthetic_batch(cfg: StepConfig, device: torch.device, generator_seed: int =
 def _optimizer(cfg: StepConfig, target, flat: bool) -> torch.optim.Optimizer:
     return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
                            weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
-                           clip_grad_norm=cfg.clip_grad_norm, trust_coefficient=cfg.trust_coefficient)
+                           clip_grad_norm=cfg.clip_grad_norm, trust_coefficient=cfg.trust_coefficient,
+                           ema_decay=cfg.ema_decay or None)
 
 
 def build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:

@@ -76,6 +76,10 @@ def save_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
     ``net`` keys with the ``module.`` prefix the reference's DataParallel
     checkpoints carry (``data_parallel.py:143-155``), so its
     ``net.load_state_dict(checkpoint['net'])`` accepts our files too.
+
+    When the optimizer keeps a weight EMA (``ema_decay``), ``net_ema`` holds
+    the model's state dict with the averaged weights in place of the live ones
+    (same keys and prefix as ``net``; buffers are the live ones).
     """
     if not all_ranks and _rank() != 0:
         return None
@@ -83,8 +87,14 @@ def save_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
     net = unwrap(model).state_dict()
     if module_prefix is None:
         module_prefix = unwrap(model) is not model
+    net_ema = None
+    if optimizer is not None and getattr(optimizer, "ema_enabled", False):
+        with optimizer.ema_weights():  # the clone must be taken inside: the tensors are the flats' views
+            net_ema = {k: v.detach().clone() for k, v in unwrap(model).state_dict().items()}
     if module_prefix:
         net = {"module." + k: v for k, v in net.items()}
+        if net_ema is not None:
+            net_ema = {"module." + k: v for k, v in net_ema.items()}
     state = {
         "net": net,
         "acc": best_acc,
@@ -94,6 +104,8 @@ def save_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
         "rng": rng_state(),
         "extra": extra or {},
     }
+    if net_ema is not None:
+        state["net_ema"] = net_ema
     tmp = f"{path}.tmp.{os.getpid()}"
     torch.save(state, tmp)
     os.replace(tmp, path)
@@ -141,16 +153,23 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
     return {"epoch": state.get("epoch", 0), "acc": state.get("acc", 0.0), "extra": state.get("extra", {})}
 
 
-def load_weights(path: str, model: nn.Module, map_location=None) -> Dict[str, Any]:
+def load_weights(path: str, model: nn.Module, map_location=None, ema: bool = False) -> Dict[str, Any]:
     """Initialise `model` from the weights of a checkpoint (fine-tuning): the
-    ``net`` entry only -- no optimizer, scheduler or RNG state, and the
-    checkpoint's epoch / accuracy do not carry over.  A ViT ``pos_embedding``
+    ``net`` entry only (``ema=True``: the averaged weights, ``net_ema``; an
+    error when the file has none) -- no optimizer, scheduler or RNG state, and
+    the checkpoint's epoch / accuracy do not carry over.  A ViT ``pos_embedding``
     of another token count is resized onto the model's patch grid
     (``models.vit.resize_pos_embedding``); any other mismatch raises.  Call it
     before the optimizer is built, so fp32 master weights start from the
     loaded values."""
     state = _load_weights_only(path, map_location or "cpu")
-    sd = dict(_strip_prefix(state["net"] if isinstance(state, dict) and "net" in state else state))
+    if ema:
+        if not isinstance(state, dict) or state.get("net_ema") is None:
+            raise KeyError(f"load_weights(ema=True): {path} has no averaged weights ('net_ema'); it was "
+                           "written by a run without a weight EMA (--model-ema-decay)")
+        sd = dict(_strip_prefix(state["net_ema"]))
+    else:
+        sd = dict(_strip_prefix(state["net"] if isinstance(state, dict) and "net" in state else state))
     target = unwrap(model)
     own = target.state_dict()
     resized = False

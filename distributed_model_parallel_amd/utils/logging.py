@@ -20,11 +20,12 @@ from typing import Any, Dict, Optional
 def reference_line(epoch: int, rec: Dict[str, Any]) -> str:
     """``step:E  loss_train:..  acc1_train:..  loss_val:..  acc1_val:..[  time_per_batch:..
     time_load_perbatch:..]`` exactly in the reference's key order; ``grad_norm`` follows
-    when the run clips gradients, ``trust_min`` / ``trust_max`` under LARS (the reference
-    has no such fields)."""
+    when the run clips gradients, ``trust_min`` / ``trust_max`` under LARS, ``loss_val_ema`` /
+    ``acc1_val_ema`` / ``ema_decay`` when it keeps a weight EMA (the reference has no such fields)."""
     parts = [f"step:{epoch}"]
     for k in ("loss_train", "acc1_train", "loss_val", "acc1_val", "time_per_batch",
-              "time_load_perbatch", "grad_norm", "trust_min", "trust_max"):
+              "time_load_perbatch", "grad_norm", "trust_min", "trust_max", "loss_val_ema", "acc1_val_ema",
+              "ema_decay"):
         if k in rec and rec[k] is not None:
             parts.append(f"{k}:{rec[k]}")
     return "  ".join(parts)
