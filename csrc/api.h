@@ -190,6 +190,11 @@ at::Tensor wgrad3x3(const at::Tensor& dy, const at::Tensor& x, int64_t stride);
 bool wgrad3x3_supported(int64_t C, int64_t H, int64_t W, int64_t stride);
 void set_wgrad3x3_waves(int64_t nw);
 
+// ---- data/augment.hip ----
+at::Tensor augment_batch(const at::Tensor& src, const at::Tensor& plan, int64_t out_h, int64_t out_w,
+                         const std::vector<double>& mean, const std::vector<double>& std_, at::ScalarType dtype,
+                         bool channels_last, bool no_resize);
+
 // ---- data/batch_mix.hip ----
 at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, const std::vector<int64_t>& box);
 

@@ -71,6 +71,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mixup (empty box): lam * x[i] + (1 - lam) * x[perm[i]]; CutMix (box = [y0, y1, x0, x1]): "
         "x[perm[i]] inside the box, x[i] outside; channels-last bf16 / fp32, out of place",
         py::call_guard<py::gil_scoped_release>());
+  m.def("augment_batch", &dmp::augment_batch, py::arg("src"), py::arg("plan"), py::arg("out_h"), py::arg("out_w"),
+        py::arg("mean"), py::arg("std"), py::arg("dtype"), py::arg("channels_last") = true, py::arg("no_resize") = false,
+        "uint8 NHWC batch -> [B, C, out_h, out_w] bf16 / fp32: per-sample crop box plan[i] = (x0, y0, cw, ch, flip) "
+        "(zero padding outside the image, bilinear resize when the box is not out_h x out_w), flip, /255, "
+        "mean / std normalisation, cast and layout in one launch; no_resize: every box is out_h x out_w (the crop-only kernel; "
+        "other rows come out NaN)",
+        py::call_guard<py::gil_scoped_release>());
   m.def("gemm_nt_bnbwd", &dmp::gemm_nt_bnbwd, py::arg("A"), py::arg("B"), py::arg("residual"),
         py::arg("bn_x"), py::arg("bn_y"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("bias"), py::arg("res_map") = std::vector<int64_t>{}, py::arg("a2") = py::none(),

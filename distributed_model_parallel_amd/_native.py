@@ -103,6 +103,8 @@ FEATURES = {
                             "(stem_halo.hip stem_halo_wgrad_pool) -> maxpool2d_bn_backward + two stem_halo_wgrad",
     "fuse_ema": "weight EMA updated inside the flat optimizers' step kernels (ops/optim.py ema_decay) "
                 "-> the step kernel + a lerp_ pass over the masters",
+    "gpu_augment": "crop / resize / flip / normalise / cast / layout of a uint8 batch in one kernel (augment.hip, "
+                   "data/gpu_augment.py) -> the PyTorch composition, sample by sample",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",
 }

@@ -33,17 +33,23 @@ def pil_loader(path: str):
 
 # --------------------------------------------------------------------------- #
 class SyntheticImages(Dataset):
-    """Deterministic random images/labels (shape of ImageNet or CIFAR)."""
+    """Deterministic random images/labels (shape of ImageNet or CIFAR).  ``uint8=True``: HWC
+    ``uint8`` images of that shape, what a decoding-only loader hands the GPU augmentation path."""
 
     def __init__(self, length: int, shape=(3, 224, 224), num_classes: int = 1000, seed: int = 0,
-                 dtype=torch.float32):
+                 dtype=torch.float32, uint8: bool = False):
         self.length, self.shape, self.num_classes, self.seed, self.dtype = length, tuple(shape), num_classes, seed, dtype
+        self.uint8 = uint8
 
     def __len__(self):
         return self.length
 
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
+        if self.uint8:
+            c, h, w = self.shape
+            return (torch.randint(0, 256, (h, w, c), generator=g, dtype=torch.uint8),
+                    int(torch.randint(0, self.num_classes, (1,), generator=g)))
         return (torch.randn(self.shape, generator=g).to(self.dtype),
                 int(torch.randint(0, self.num_classes, (1,), generator=g)))
 

@@ -4,8 +4,11 @@ Covers the reference's pipelines: CIFAR-10 ``RandomCrop(32, padding=4) +
 RandomHorizontalFlip + ToTensor + Normalize`` (``model_parallel.py:77-87``)
 and the ImageNet-style ``RandomResizedCrop / Resize + CenterCrop``.  Inputs
 are PIL images or uint8 HWC numpy arrays; ``ToTensor`` yields float CHW in
-[0, 1].  The GPU-side alternative (crop/flip/normalise/cast/layout in one HIP
-kernel) is :func:`..data.gpu_augment.gpu_augment`.
+[0, 1].  The GPU-side alternative (crop/resize/flip/normalise/cast/layout in
+one HIP kernel, ``csrc/data/augment.hip``) is
+:func:`distributed_model_parallel_amd.data.gpu_augment.gpu_augment`: the
+``*_staging_transform`` pipelines below only decode (and, for ImageNet-style
+sets, bring every image to one staging square) and end in ``ToUint8``.
 """
 from __future__ import annotations
 
@@ -150,3 +153,20 @@ def imagenet_train_transform(size: int = 224):
 def imagenet_val_transform(size: int = 224):
     return Compose([Resize(int(size * 256 / 224)), CenterCrop(size), ToTensor(),
                     Normalize(IMAGENET_MEAN, IMAGENET_STD)])
+
+
+# Staging pipelines of the GPU augmentation path: uint8 HWC of one fixed shape
+# per dataset (the default collate stacks them); the crop / resize / flip /
+# normalisation happen on the device (data/gpu_augment.py).
+def cifar_staging_transform():
+    return ToUint8()
+
+
+def imagenet_train_staging_transform(staging: int = 256):
+    """The central `staging` square of the image resized to shorter side `staging`:
+    the random resized crops are then drawn from that square, not from the full image."""
+    return Compose([Resize(staging), CenterCrop(staging), ToUint8()])
+
+
+def imagenet_val_staging_transform(size: int = 224):
+    return Compose([Resize(int(size * 256 / 224)), CenterCrop(size), ToUint8()])

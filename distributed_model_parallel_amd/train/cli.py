@@ -99,6 +99,14 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
                          "are mutually exclusive")
         if args.parallel == "pipe":
             parser.error("--init-from with --parallel pipe is not supported")
+    if args.augment_staging is not None and not args.gpu_augment:
+        parser.error("--augment-staging needs --gpu-augment")
+    if args.gpu_augment:
+        if args.parallel == "pipe":
+            parser.error("--gpu-augment with --parallel pipe is not supported "
+                         "(the pipeline's first-stage feed takes finished images)")
+        if args.augment_staging is not None and not 1 <= args.augment_staging <= 16384:
+            parser.error("--augment-staging must be in [1, 16384]")
     world = args.world_size or int(os.environ.get("WORLD_SIZE", "1"))
     if args.clip_grad_norm and args.parallel == "pipe" and world > 1:
         parser.error("--clip-grad-norm with --parallel pipe at world size > 1 is not supported "
@@ -196,6 +204,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="NHWC activations (default on GPU: every native conv/BN kernel is NHWC)")
     p.add_argument("--no-channels-last", dest="channels_last", action="store_false")
     p.add_argument("--synthetic", action="store_true")
+    p.add_argument("--gpu-augment", action="store_true",
+                   help="loader workers only decode to uint8; the batch goes up as bytes and one kernel crops "
+                        "(CIFAR-type sets: pad 4 + random crop; otherwise random resized crop), flips, normalises, "
+                        "casts and lays out (data/gpu_augment.py); validation takes the same kernel with the "
+                        "identity plan; not with --parallel pipe")
+    p.add_argument("--augment-staging", default=None, type=int, metavar="S",
+                   help="--gpu-augment, ImageNet-style sets: workers resize the shorter side to S and keep the "
+                        "central S x S square, from which the random resized crops are drawn "
+                        "(default round(size * 8 / 7): 256 for 224, 439 for 384)")
     p.add_argument("--micro-batches", default=1, type=int)
     p.add_argument("--no-pipe-graphs", action="store_true",
                    help="--parallel pipe on GPU: eager micro-batches instead of captured stage graphs")
@@ -219,9 +236,33 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def _augment_geometry(args):
+    """(CIFAR-type?, output side, training source side) of the --gpu-augment path: CIFAR-type sets
+    crop their own 32 x 32 images with padding, the others resize crops of the staging square."""
+    synthetic = args.synthetic or not args.data
+    cifar = (_synthetic_kind(args) == "SyntheticCIFAR") if synthetic else args.dataset_type == "CIFAR10"
+    size = args.image_size if args.image_size is not None else (32 if cifar else 224)
+    if cifar:
+        return True, size, size if synthetic else 32  # the CIFAR-10 files hold 32 x 32 images
+    return False, size, args.augment_staging if args.augment_staging is not None else round(size * 8 / 7)
+
+
 def _datasets(args):
     from ..data import DatasetCollection, transforms as T
     cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
+    if getattr(args, "gpu_augment", False):  # uint8 HWC: decoded (and staged) only
+        from ..data import SyntheticImages
+        is_cifar, size, source = _augment_geometry(args)
+        if args.synthetic or not args.data:
+            nc = _num_classes(args)
+            n_train, n_val = (5000, 1000) if is_cifar else (1281, 500)
+            return (SyntheticImages(n_train, (3, source, source), nc, uint8=True),
+                    SyntheticImages(n_val, (3, size, size), nc, seed=1, uint8=True))
+        if is_cifar:
+            tr = va = T.cifar_staging_transform()
+        else:
+            tr, va = T.imagenet_train_staging_transform(source), T.imagenet_val_staging_transform(size)
+        return DatasetCollection(args.dataset_type, args.data, tr, va).init()
     if args.synthetic or not args.data:
         if args.image_size is not None:  # the stock synthetic sets, at the ViT's own resolution
             from ..data import SyntheticImages
@@ -321,6 +362,25 @@ def run_data_parallel(args, env) -> None:
             x = x.contiguous(memory_format=torch.channels_last)
         return x, y.to(dev, non_blocking=True)
 
+    to_dev_val = to_dev  # without --gpu-augment validation batches go up as training batches do
+    planner = None
+    if args.gpu_augment:  # the batch goes up as bytes; crop / flip / normalise / cast / layout in one kernel
+        from ..data import AugmentPlanner, gpu_augment, transforms as T
+        is_cifar, size, source = _augment_geometry(args)
+        mean, std = (T.CIFAR_MEAN, T.CIFAR_STD) if is_cifar else (T.IMAGENET_MEAN, T.IMAGENET_STD)
+        planner = AugmentPlanner("pad_crop" if is_cifar else "rrc", size, source, seed=args.seed,
+                                 rank=env.rank if args.parallel == "ddp" else 0)
+        eval_planner = AugmentPlanner("identity", size, size)
+
+        def augment_to_dev(plans):
+            def feed(x, y):
+                x = gpu_augment(x.to(dev, non_blocking=True), plans.plan(x.shape[0]), size, mean, std, dtype=dtype,
+                                channels_last=bool(args.channels_last))
+                return x, y.to(dev, non_blocking=True)
+            return feed
+
+        to_dev, to_dev_val = augment_to_dev(planner), augment_to_dev(eval_planner)
+
     mixer = None
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         from ..ops.mix import BatchMixer
@@ -330,6 +390,8 @@ def run_data_parallel(args, env) -> None:
     for epoch in range(start_epoch, args.epochs):
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if planner is not None:
+            planner.set_epoch(epoch)
         if mixer is not None:
             mixer.set_epoch(epoch)
         net.train()
@@ -358,11 +420,11 @@ def run_data_parallel(args, env) -> None:
             torch.cuda.synchronize()
         tm = timer.summary()  # device time of the step (HIP events), host time of the data wait
         step_s, data_s = tm.get("step", 0.0) / 1e3, tm.get("data_host", 0.0) / 1e3
-        vl, va = evaluate(net, val_loader, to_dev, args)
+        vl, va = evaluate(net, val_loader, to_dev_val, args)
         ema_log, ck_extra = {}, None
         if args.model_ema_decay:  # the averaged weights on the live buffers (BN statistics are not averaged)
             with opt.ema_weights():
-                vle, vae = evaluate(net, val_loader, to_dev, args)
+                vle, vae = evaluate(net, val_loader, to_dev_val, args)
             ema_log = {"loss_val_ema": vle, "acc1_val_ema": vae, "ema_decay": args.model_ema_decay}
             ck_extra = {"acc_ema": float(vae)}
         sched.step()
