@@ -1,0 +1,166 @@
+"""Plain fp64 references for the depthwise and pooling kernels, on whatever
+device the inputs live on, plus the integer geometry of the depthwise host code.
+
+Two kinds of comparison use them (tests/test_gpu_depthwise_edges.py,
+tests/test_gpu_pool_edges.py):
+  * integer-valued inputs, where every fp32 partial sum is an integer below
+    2^24 and every bf16 output an integer of magnitude at most 256: the kernel
+    must then equal the fp64 reference bit for bit;
+  * real-valued inputs, where the bound is U * (sum of |products|) from fp32
+    fused-multiply-add accumulation -- the ``*_abs`` functions give that sum.
+tests/test_exact_ref_cpu.py checks the references themselves against PyTorch
+autograd in fp64 on the CPU."""
+import torch
+import torch.nn.functional as F
+
+U = 2.0 ** -24        # fp32 unit roundoff
+BF16_HALF_ULP = 2.0 ** -8  # half a bf16 ulp at the bottom of a binade, relative
+
+
+# ---------------------------------------------------------------------------
+# depthwise 3x3, padding 1, stride 1 or 2; x [N,C,H,W], w [C,1,3,3], all fp64
+# ---------------------------------------------------------------------------
+def dw_out(size, stride):
+    return (size + 2 - 3) // stride + 1
+
+
+def _tap_view(t, kh, kw, oh, ow, s):
+    """The [N,C,oh,ow] view of the padded tensor that tap (kh, kw) reads."""
+    return t[:, :, kh:kh + (oh - 1) * s + 1:s, kw:kw + (ow - 1) * s + 1:s]
+
+
+def dw_forward(x, w, stride):
+    x, w = x.double(), w.double()
+    n, c, h, wd = x.shape
+    oh, ow = dw_out(h, stride), dw_out(wd, stride)
+    xp = F.pad(x, (1, 1, 1, 1))
+    y = torch.zeros(n, c, oh, ow, dtype=torch.float64, device=x.device)
+    for kh in range(3):
+        for kw in range(3):
+            y += _tap_view(xp, kh, kw, oh, ow, stride) * w[:, 0, kh, kw].view(1, c, 1, 1)
+    return y
+
+
+def dw_dgrad(dy, w, stride, h, wd):
+    dy, w = dy.double(), w.double()
+    n, c, oh, ow = dy.shape
+    assert (oh, ow) == (dw_out(h, stride), dw_out(wd, stride))
+    dxp = torch.zeros(n, c, h + 2, wd + 2, dtype=torch.float64, device=dy.device)
+    for kh in range(3):
+        for kw in range(3):
+            _tap_view(dxp, kh, kw, oh, ow, stride).add_(dy * w[:, 0, kh, kw].view(1, c, 1, 1))
+    return dxp[:, :, 1:h + 1, 1:wd + 1].contiguous()
+
+
+def dw_wgrad(dy, x, stride):
+    dy, x = dy.double(), x.double()
+    n, c, oh, ow = dy.shape
+    assert (oh, ow) == (dw_out(x.shape[2], stride), dw_out(x.shape[3], stride))
+    xp = F.pad(x, (1, 1, 1, 1))
+    dw = torch.zeros(c, 1, 3, 3, dtype=torch.float64, device=x.device)
+    for kh in range(3):
+        for kw in range(3):
+            dw[:, 0, kh, kw] = (_tap_view(xp, kh, kw, oh, ow, stride) * dy).sum(dim=(0, 2, 3))
+    return dw
+
+
+def dw_forward_abs(x, w, stride):
+    return dw_forward(x.double().abs(), w.double().abs(), stride)
+
+
+def dw_dgrad_abs(dy, w, stride, h, wd):
+    return dw_dgrad(dy.double().abs(), w.double().abs(), stride, h, wd)
+
+
+def dw_wgrad_abs(dy, x, stride):
+    return dw_wgrad(dy.double().abs(), x.double().abs(), stride)
+
+
+def dw_split(n, c, h, w, stride, dtype):
+    """The integers the depthwise host code derives (csrc/conv/depthwise.hip
+    make_geo and the weight-gradient work split), recomputed so that a test
+    which exists to reach a branch can assert that it still does."""
+    vec = 8 if dtype == torch.bfloat16 else 4
+    tw = 4
+    g = {"vec": vec, "OH": dw_out(h, stride), "OW": dw_out(w, stride), "cv": c // vec}
+    g["tc"] = min(g["cv"], 256)
+    g["spp"] = 256 // g["tc"]
+    g["idle"] = 256 - g["spp"] * g["tc"]
+    g["strips"] = -(-g["OW"] // tw)
+    g["cchunks"] = -(-g["cv"] // g["tc"])
+    g["last_chunk_lanes"] = g["cv"] - (g["cchunks"] - 1) * g["tc"]
+    g["total"] = n * g["OH"] * g["strips"]
+    g["passes"] = -(-g["total"] // g["spp"])          # forward grid.x = moment partial rows
+    target = max(1, 1024 // g["cchunks"])
+    g["spl"] = max(1, -(-g["passes"] // target))      # strips_per_lane
+    g["wgrid"] = -(-g["passes"] // g["spl"])
+    # lanes of the weight-gradient grid that find sidx >= total and break
+    g["wgrad_past_total"] = g["wgrid"] * g["spl"] * g["spp"] - g["total"]
+    return g
+
+
+# ---------------------------------------------------------------------------
+# max pooling; taps as the kernels store them: one byte per [N,Ho,Wo,C] element
+# ---------------------------------------------------------------------------
+def pool_out(size, k, s, p):
+    return (size + 2 * p - k) // s + 1
+
+
+def pool_forward(x, k, s, p):
+    """(y, taps) from CPU PyTorch on an NCHW fp32 copy of x [N,C,H,W] (bf16 and
+    fp32 are both exact in it): y [N,C,Ho,Wo] fp32, taps [N,Ho,Wo,C] int64 with
+    tap = (ih - (oh*s - p)) * k + (iw - (ow*s - p)), both on x's device.  First
+    maximum in window order; an all -inf window gives its first in-bounds tap;
+    with one NaN in a window the NaN wins."""
+    xc = x.detach().float().cpu().contiguous()
+    n, c, h, w = xc.shape
+    y, ind = F.max_pool2d(xc, k, s, p, return_indices=True)
+    ho, wo = y.shape[2], y.shape[3]
+    assert (ho, wo) == (pool_out(h, k, s, p), pool_out(w, k, s, p))
+    ih, iw = ind // w, ind % w
+    oh = torch.arange(ho).view(1, 1, ho, 1)
+    ow = torch.arange(wo).view(1, 1, 1, wo)
+    a, b = ih - (oh * s - p), iw - (ow * s - p)
+    assert bool(((a >= 0) & (a < k) & (b >= 0) & (b < k)).all())
+    taps = (a * k + b).permute(0, 2, 3, 1).contiguous()
+    return y.to(x.device), taps.to(x.device)
+
+
+def pool_scatter(dy, taps, h, w, k, s, p):
+    """dx [N,C,H,W] fp64: every dy[n,c,oh,ow] added to the input pixel its tap names."""
+    n, c, ho, wo = dy.shape
+    dev = dy.device
+    taps = taps.to(dev).long().view(n, ho, wo, c)
+    oh = torch.arange(ho, device=dev).view(1, ho, 1, 1)
+    ow = torch.arange(wo, device=dev).view(1, 1, wo, 1)
+    ih = oh * s - p + taps // k
+    iw = ow * s - p + taps % k
+    assert bool(((ih >= 0) & (ih < h) & (iw >= 0) & (iw < w)).all()), "a tap names a padding pixel"
+    nn_ = torch.arange(n, device=dev).view(n, 1, 1, 1).expand_as(taps)
+    cc = torch.arange(c, device=dev).view(1, 1, 1, c).expand_as(taps)
+    flat = ((nn_ * c + cc) * h + ih) * w + iw
+    dx = torch.zeros(n * c * h * w, dtype=torch.float64, device=dev)
+    dx.index_add_(0, flat.reshape(-1), dy.double().permute(0, 2, 3, 1).reshape(-1))
+    return dx.view(n, c, h, w)
+
+
+def bn_relu_pool_forward(x, scale, shift, k, s, p):
+    """maxpool(bf16(relu(x * scale + shift))) with the affine in fp64: (y, taps)
+    as pool_forward gives them.  The caller chooses x, scale and shift so that
+    the affine is exact in fp32 too (tests/test_gpu_pool_edges.py)."""
+    c = x.shape[1]
+    z = torch.relu(x.double() * scale.double().view(1, c, 1, 1) + shift.double().view(1, c, 1, 1))
+    z32 = z.float()
+    assert bool((z32.double() == z).all()), "the affine is not exact in fp32"
+    return pool_forward(z32.bfloat16(), k, s, p)
+
+
+def bn_pool_backward(dy, taps, x, scale, shift, mean, k, s, p):
+    """(dz [N,C,H,W] fp64, sum dz [C], sum dz*(x-mean) [C]) of the fused BN+ReLU+pool
+    backward: the pool gradient rounded to bf16, masked by relu'(x*scale+shift)."""
+    n, c, h, w = x.shape
+    g = pool_scatter(dy, taps, h, w, k, s, p).float().bfloat16().double()
+    x64 = x.double()
+    on = x64 * scale.double().view(1, c, 1, 1) + shift.double().view(1, c, 1, 1) > 0
+    dz = torch.where(on, g, torch.zeros_like(g))
+    return dz, dz.sum(dim=(0, 2, 3)), (dz * (x64 - mean.double().view(1, c, 1, 1))).sum(dim=(0, 2, 3))

@@ -14,7 +14,9 @@ pytestmark = pytest.mark.gpu
                                          ((2, 24, 8, 8), 5, 3, 2)])
 def test_maxpool_matches_torch(dtype, shape, k, s, p):
     torch.manual_seed(0)
-    # distinct values per window so argmax ties cannot differ in tie-breaking
+    # randn rounded to bf16 repeats values within a window now and then, so this
+    # also leans on first-maximum tie-breaking; tests/test_gpu_pool_edges.py
+    # compares the argmax bytes themselves on inputs made of ties
     x = torch.randn(*shape, device="cuda").to(dtype).contiguous(memory_format=torch.channels_last)
     xi = x.detach().requires_grad_()
     xr = x.detach().float().requires_grad_()

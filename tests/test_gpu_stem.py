@@ -172,8 +172,9 @@ def test_stem_bn_backward_folded_into_wgrad(shift):
 
 @pytest.mark.parametrize("n,c,h,w", [(3, 64, 16, 16), (2, 32, 14, 10), (2, 64, 9, 11), (1, 128, 8, 8)])
 def test_bn_pool_backward_kernel_vs_fp32(n, c, h, w):
-    """maxpool2d_bn_backward (quad kernel for even H/W, one-pixel kernel for odd)
-    against an fp32 scatter of dy through the forward's argmax taps."""
+    """maxpool2d_bn_backward (one kernel, one input pixel x 8 channels per lane,
+    for even and odd H/W) against an fp32 scatter of dy through the forward's
+    argmax taps."""
     from distributed_model_parallel_amd import _native
     C = _native.require("bn pool backward")
     torch.manual_seed(0)
