@@ -12,6 +12,7 @@
 #include <c10/util/Optional.h>
 
 #include <cstdint>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -125,6 +126,12 @@ at::Tensor dwconv3x3_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t st
                            int64_t W);
 at::Tensor dwconv3x3_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t stride,
                            at::ScalarType out_dtype, const c10::optional<at::Tensor>& out);
+
+// ---- conv/depthwise7.hip ----
+at::Tensor dwconv7x7_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias);
+at::Tensor dwconv7x7_dgrad(const at::Tensor& dy, const at::Tensor& w, const c10::optional<at::Tensor>& add);
+std::vector<at::Tensor> dwconv7x7_wgrad(const at::Tensor& dy, const at::Tensor& x, at::ScalarType w_dtype);
+std::map<std::string, int64_t> dwconv7x7_plan(int64_t N, int64_t C, int64_t H, int64_t W);
 
 // ---- conv/gemm_bf16.hip ----
 std::vector<at::Tensor> gemm_nt(const at::Tensor& A, const at::Tensor& B,

@@ -305,6 +305,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_dtype"), py::arg("out") = py::none(),
         py::call_guard<py::gil_scoped_release>());
 
+  m.def("dwconv7x7_forward", &dmp::dwconv7x7_forward, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dwconv7x7_dgrad", &dmp::dwconv7x7_dgrad, py::arg("dy"), py::arg("w"), py::arg("add") = py::none(),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dwconv7x7_wgrad", &dmp::dwconv7x7_wgrad, py::arg("dy"), py::arg("x"), py::arg("w_dtype"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dwconv7x7_plan", &dmp::dwconv7x7_plan, py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"));
+
   // ---- optimizer ----
   m.def("sgd_flat_step", &dmp::sgd_flat_step, py::arg("master"), py::arg("mom"), py::arg("grad"),
         py::arg("param"), py::arg("lr"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"),

@@ -250,12 +250,12 @@ void launch_colsum(const at::Tensor& dy, const at::Tensor* h, at::Tensor* dh, at
 void check_2d(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kBFloat16, name,
               " must be a contiguous bf16 GPU tensor");
-  TORCH_CHECK(t.dim() >= 1 && t.size(-1) % 256 == 0, name, ": last dim must be a multiple of 256");
+  TORCH_CHECK(t.dim() >= 1 && t.size(-1) > 0 && t.size(-1) % 64 == 0, name, ": last dim must be a multiple of 64");
 }
 
 }  // namespace
 
-bool colsum_supported(int64_t N) { return N > 0 && N % 256 == 0; }
+bool colsum_supported(int64_t N) { return N > 0 && N % 64 == 0; }
 
 // Bias gradient: dy [..., N] bf16 -> sum over all leading dims, in out_dtype.
 at::Tensor bias_grad(const at::Tensor& dy, at::ScalarType out_dtype) {

@@ -1,4 +1,4 @@
-"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16."""
+"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B."""
 from __future__ import annotations
 
 from typing import Callable, Dict
@@ -8,6 +8,7 @@ import torch.nn as nn
 from .mobilenetv2 import (HeadPool, InvertedResidual, MobileNetV2, mobilenet_v2, mobilenet_v2_224,
                           mobilenet_v2_nobn)
 from .resnet import BasicBlock, Bottleneck, ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
+from .convnext import ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, convnext_test, convnext_tiny
 from .vit import VisionTransformer, vit_b_16, vit_tiny
 
 MODELS: Dict[str, Callable[..., nn.Module]] = {
@@ -21,6 +22,10 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
     "resnet152": resnet152,
     "vit_b_16": vit_b_16,
     "vit_tiny": vit_tiny,
+    "convnext_tiny": convnext_tiny,
+    "convnext_small": convnext_small,
+    "convnext_base": convnext_base,
+    "convnext_test": convnext_test,
 }
 
 # Default input geometry per model (C, H, W) and class count.
@@ -35,6 +40,10 @@ INPUT_SHAPES = {
     "resnet152": ((3, 224, 224), 1000),
     "vit_b_16": ((3, 224, 224), 1000),
     "vit_tiny": ((3, 32, 32), 10),
+    "convnext_tiny": ((3, 224, 224), 1000),
+    "convnext_small": ((3, 224, 224), 1000),
+    "convnext_base": ((3, 224, 224), 1000),
+    "convnext_test": ((3, 32, 32), 10),
 }
 
 
@@ -48,4 +57,5 @@ def build_model(name: str, **kw) -> nn.Module:
 __all__ = ["MODELS", "INPUT_SHAPES", "build_model", "MobileNetV2", "InvertedResidual", "HeadPool",
            "mobilenet_v2", "mobilenet_v2_nobn", "mobilenet_v2_224", "ResNet", "BasicBlock", "Bottleneck", "resnet18",
            "resnet34", "resnet50", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
-           "vit_tiny"]
+           "vit_tiny", "ConvNeXt", "ConvNeXtBlock", "convnext_tiny", "convnext_small", "convnext_base",
+           "convnext_test"]

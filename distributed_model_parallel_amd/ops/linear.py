@@ -30,7 +30,12 @@
   and the bias gradient in one pass over ``dy`` (``rowscale_bias_grad``).
   ``DMP_DISABLE=fuse_drop_path`` runs the same math in torch ops.
 
-CPU tensors, non-bf16 dtypes and widths that are not a multiple of 256 use
+* ``mlp_residual_w``: ``mlp_residual`` on weight tensors, for operands formed
+  per step (ConvNeXt folds its layer scale into fc2's weight and bias); the
+  caller passes fc2's transpose, so the temporary never reaches
+  ``ops/wt_cache.py``.
+
+CPU tensors, non-bf16 dtypes and widths that are not a multiple of 64 use
 the plain PyTorch ops (same math)."""
 from __future__ import annotations
 
@@ -244,36 +249,45 @@ class _LinearResidualFn(torch.autograd.Function):
         return dx, dy, dw, db
 
 
+def _w2_t(w2: torch.Tensor, w2_t: Optional[torch.Tensor]) -> torch.Tensor:
+    """fc2's W^T [hidden, dim] for its data gradient: the caller's (a weight
+    formed per step, which the (data_ptr, shape)-keyed cache must never see) or
+    the cached transpose of the parameter."""
+    if w2_t is not None:
+        return w2_t
+    from .wt_cache import transposed
+    return transposed(w2)
+
+
 class _MLPResidualFn(torch.autograd.Function):
     """y = res + fc2(gelu(fc1(x))) on three fused-epilogue GEMMs:
     fc1 -> (h, gelu(h)); fc2 -> bias + residual; fc2 dgrad -> * gelu'(h)."""
 
     @staticmethod
-    def forward(ctx, x, res, w1, b1, w2, b2):
+    def forward(ctx, x, res, w1, b1, w2, b2, w2_t=None):
         C = _native.require("mlp_residual")
         x2, r2 = _rows(x), _rows(res)
         h = torch.empty(x2.shape[0], w1.shape[0], dtype=x2.dtype, device=x2.device)
         a = C.gemm_xl(x2, w1, "bias_gelu", bias=b1, aux=h)
         y = C.gemm_xl(a, w2, "bias_res", bias=b2, residual=r2)
-        ctx.save_for_backward(x2, w1, h, a, w2)
+        ctx.save_for_backward(x2, w1, h, a, w2, w2_t)
         ctx.xshape = x.shape
         return y.view(res.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w1, h, a, w2 = ctx.saved_tensors
+        x2, w1, h, a, w2, w2_t = ctx.saved_tensors
         C = _native.require("mlp_residual backward")
         dy2 = _rows(dy)
         db2 = C.bias_grad(dy2, w2.dtype)
         dw2 = _wgrad(dy2, a, w2)
         # dh = bf16(bf16(dy @ W2) * gelu'(h)): B operand is W2^T [hidden, dim]
         # and fc1's bias gradient (column sums of dh) from the same epilogue
-        from .wt_cache import transposed
-        dh, db1 = C.gemm_xl_dgelu_bgrad(dy2, transposed(w2), h)
+        dh, db1 = C.gemm_xl_dgelu_bgrad(dy2, _w2_t(w2, w2_t), h)
         db1 = db1.to(w1.dtype)
         dw1 = _wgrad(dh, x2, w1)
         dx = _dgrad(dh, w1)
-        return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2
+        return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2, None
 
 
 class _LinearResidualScaleFn(torch.autograd.Function):
@@ -306,29 +320,28 @@ class _MLPResidualScaleFn(torch.autograd.Function):
     backward runs on g = s * dy (rowscale_bias_grad) where that one runs on dy."""
 
     @staticmethod
-    def forward(ctx, x, res, w1, b1, w2, b2, s):
+    def forward(ctx, x, res, w1, b1, w2, b2, s, w2_t=None):
         C = _native.require("mlp_residual (row_scale)")
         x2, r2 = _rows(x), _rows(res)
         ctx.rps = x2.shape[0] // s.numel()
         h = torch.empty(x2.shape[0], w1.shape[0], dtype=x2.dtype, device=x2.device)
         a = C.gemm_xl(x2, w1, "bias_gelu", bias=b1, aux=h)
         y = C.gemm_xl(a, w2, "bias_res_scale", bias=b2, residual=r2, row_scale=s, rows_per_sample=ctx.rps)
-        ctx.save_for_backward(x2, w1, h, a, w2, s)
+        ctx.save_for_backward(x2, w1, h, a, w2, s, w2_t)
         ctx.xshape = x.shape
         return y.view(res.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w1, h, a, w2, s = ctx.saved_tensors
+        x2, w1, h, a, w2, s, w2_t = ctx.saved_tensors
         C = _native.require("mlp_residual backward (row_scale)")
         g, db2 = C.rowscale_bias_grad(_rows(dy), s, ctx.rps, w2.dtype)
         dw2 = _wgrad(g, a, w2)
-        from .wt_cache import transposed
-        dh, db1 = C.gemm_xl_dgelu_bgrad(g, transposed(w2), h)
+        dh, db1 = C.gemm_xl_dgelu_bgrad(g, _w2_t(w2, w2_t), h)
         db1 = db1.to(w1.dtype)
         dw1 = _wgrad(dh, x2, w1)
         dx = _dgrad(dh, w1)
-        return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2, None
+        return dx.view(ctx.xshape), dy, dw1, db1, dw2, db2, None, None
 
 
 def _scale_ok(x: torch.Tensor, res: torch.Tensor, row_scale: torch.Tensor) -> bool:
@@ -380,3 +393,29 @@ def mlp_residual(x: torch.Tensor, res: torch.Tensor, fc1: nn.Linear, fc2: nn.Lin
         return _MLPResidualFn.apply(x, res, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
     hdn = F.dropout(linear_gelu(x, fc1.weight, fc1.bias), dropout, training)
     return res + F.dropout(linear(hdn, fc2.weight, fc2.bias), dropout, training)
+
+
+def mlp_residual_w(x: torch.Tensor, res: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor],
+                   w2: torch.Tensor, b2: Optional[torch.Tensor], row_scale: Optional[torch.Tensor] = None,
+                   w2_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mlp_residual`` on tensors (no dropout): res + [row_scale[b] *] (gelu(x @ w1^T + b1) @ w2^T + b2).
+
+    For weights formed per step (ConvNeXt folds its layer scale into fc2's
+    operands): ``w2`` may be a temporary with a ``grad_fn``.  Pass ``w2_t`` =
+    its transpose ``[hidden, dim]`` for the fc2 data gradient; without it the
+    transpose comes from ``ops/wt_cache.py``, which is for parameters only."""
+    ok = (b1 is not None and b2 is not None and b1.dtype == torch.bfloat16 and b2.dtype == torch.bfloat16
+          and _xl_ok(x, w1, w2) and res.dtype == torch.bfloat16
+          and (w2_t is None or (_gemm_operand_ok(w2_t) and tuple(w2_t.shape) == (w2.shape[1], w2.shape[0]))))
+    # off the fused route a temporary w2 takes the library GEMM: linear()'s data
+    # gradient would ask the cache for its transpose
+    fc2 = linear if w2.is_leaf else F.linear
+    if row_scale is not None:
+        if ok and _scale_ok(x, res, row_scale):
+            _STATS["xl"] += 1
+            return _MLPResidualScaleFn.apply(x, res, w1, b1, w2, b2, row_scale, w2_t)
+        return res + _scaled(fc2(linear_gelu(x, w1, b1), w2, b2), row_scale)
+    if ok:
+        _STATS["xl"] += 1
+        return _MLPResidualFn.apply(x, res, w1, b1, w2, b2, w2_t)
+    return res + fc2(linear_gelu(x, w1, b1), w2, b2)

@@ -10,6 +10,11 @@ gradient as a column sum -- no MIOpen ``igemm_fwd`` / ``igemm_wrw``
 (kh, kw, c) so the copy reads a channels-last image in 3-element runs and
 writes rows contiguously; the weight is permuted to match (a 1.2 MB copy).
 
+A patch vector whose length p * p * C is not a multiple of 64 (the GEMM's K
+step; the ConvNeXt stem's 4 x 4 x 3 = 48) is padded with zero columns up to
+the next multiple, in the patch rows and in the permuted weight alike, and
+the weight gradient is sliced back; multiples of 64 run exactly as before.
+
 Capability: the torchvision ``conv_proj`` of ViT-B/16 (parameter layout
 [D, C, p, p] kept, so state dicts stay compatible); design: ours.
 """
@@ -35,15 +40,32 @@ def _wmat(weight: torch.Tensor) -> torch.Tensor:
     return weight.permute(0, 2, 3, 1).reshape(d, -1).contiguous()  # [D, (kh, kw, c)]
 
 
+def _pad_cols(m: torch.Tensor, k: int) -> torch.Tensor:
+    """[R, K] -> [R, k] with zero columns appended (k >= K)."""
+    out = m.new_zeros(m.shape[0], k)
+    out[:, :m.shape[1]].copy_(m)
+    return out
+
+
 class _PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, p):
         C = _native.require("patch embed")
         b, c, h, w = x.shape
-        patches = _patchify(x, p)
-        y = C.gemm_xl(patches, _wmat(weight), "bias", bias=bias)
+        k = p * p * c
+        if k % 64 == 0:
+            patches = _patchify(x, p)
+            y = C.gemm_xl(patches, _wmat(weight), "bias", bias=bias)
+        else:  # zero columns up to the GEMM's K step
+            kp = (k + 63) // 64 * 64
+            t = x.reshape(b, c, h // p, p, w // p, p).permute(0, 2, 4, 3, 5, 1)
+            patches = x.new_zeros(b * (h // p) * (w // p), kp)
+            patches[:, :k].view(b, h // p, w // p, p, p, c).copy_(t)
+            y = C.gemm_xl(patches, _pad_cols(weight.permute(0, 2, 3, 1).reshape(weight.shape[0], -1), kp),
+                          "bias", bias=bias)
         ctx.save_for_backward(patches, weight)
         ctx.geom = (b, c, h, w, p)
+        ctx.x_cl = x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
         return y.view(b, (h // p) * (w // p), weight.shape[0])
 
     @staticmethod
@@ -59,6 +81,8 @@ class _PatchEmbedFn(torch.autograd.Function):
             from . import wgrad_stream
             with wgrad_stream.side(weight, dy2, patches):  # the layout copy follows the GEMM on S
                 dwm = _wgrad(dy2, patches, weight)  # [D, (kh, kw, c)]
+                if dwm.shape[1] != p * p * c:  # drop the zero-padded columns
+                    dwm = dwm[:, :p * p * c].contiguous()
                 dw = dwm.view(d, p, p, c).permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last) \
                     if weight.is_contiguous(memory_format=torch.channels_last) else \
                     dwm.view(d, p, p, c).permute(0, 3, 1, 2).contiguous()
@@ -66,7 +90,10 @@ class _PatchEmbedFn(torch.autograd.Function):
             db = C.bias_grad(dy2, weight.dtype)
         if ctx.needs_input_grad[0]:  # the image rarely needs a gradient: plain GEMM + un-patchify
             dp = dy2.mm(_wmat(weight)).view(b, h // p, w // p, p, p, c)
-            dx = dp.permute(0, 5, 1, 3, 2, 4).reshape(b, c, h, w)
+            if ctx.x_cl:  # a channels-last input (ConvNeXt downsampling) gets a channels-last gradient
+                dx = dp.permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, c).permute(0, 3, 1, 2)
+            else:
+                dx = dp.permute(0, 5, 1, 3, 2, 4).reshape(b, c, h, w)
         return dx, dw, db, None
 
 
@@ -86,7 +113,7 @@ class PatchEmbed(nn.Conv2d):
         from .linear import _XL, _XL_MIN_ROWS
         C = _native.native()
         return (_XL and h % p == 0 and w % p == 0 and b * (h // p) * (w // p) >= _XL_MIN_ROWS
-                and (p * p * c) % 64 == 0 and self.weight.shape[0] % 64 == 0
+                and self.weight.shape[0] % 64 == 0
                 and C.colsum_supported(self.weight.shape[0]))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -72,8 +72,9 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
     if not 0.0 <= args.drop_path < 1.0:
         parser.error("--drop-path must be in [0, 1)")
     if args.drop_path > 0:
-        if not args.arch.startswith("vit"):
-            parser.error(f"--drop-path is for ViT archs only (vit_b_16, vit_tiny), not --arch {args.arch}")
+        if not args.arch.startswith(("vit", "convnext")):
+            parser.error(f"--drop-path is for ViT archs only (vit_b_16, vit_tiny) and ConvNeXt (convnext_*), "
+                         f"not --arch {args.arch}")
     if args.image_size is not None:
         if not args.arch.startswith("vit"):
             parser.error(f"--image-size is for ViT archs only (vit_b_16, vit_tiny), not --arch {args.arch}")
@@ -172,8 +173,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mix-prob", default=None, type=float, metavar="P",
                    help="probability that a training batch is mixed (default 1.0; needs an alpha)")
     p.add_argument("--drop-path", default=0.0, type=float, metavar="R",
-                   help="ViT archs only: stochastic depth, block i of L drops its residual branches per sample "
-                        "with probability R * i / (L - 1), in [0, 1) (0 = off; e.g. 0.1 for ViT-B from scratch)")
+                   help="ViT and ConvNeXt archs only: stochastic depth, block i of L drops its residual branches per sample "
+                        "with probability R * i / (L - 1), in [0, 1) (0 = off; e.g. 0.1 for ViT-B from scratch, "
+                        "0.5 for ConvNeXt-B)")
     p.add_argument("--model-ema-decay", default=0.0, type=float, metavar="D",
                    help="keep an exponential moving average of the fp32 master weights inside the optimizer's "
                         "step kernels, decay D in [0, 1) (0 = off; e.g. 0.9999); every epoch also evaluates it "
@@ -281,8 +283,9 @@ def _datasets(args):
 
 def _synthetic_kind(args) -> str:
     """Synthetic data of the dataset type's shape -- except for a ViT, whose position
-    embedding fixes the input size: it gets data of the model's own shape and class count."""
-    if args.arch.startswith("vit"):
+    embedding fixes the input size: it gets data of the model's own shape and class count
+    (and so does a ConvNeXt: convnext_test is a 32-pixel model)."""
+    if args.arch.startswith(("vit", "convnext")):
         from ..models import INPUT_SHAPES
         return "SyntheticCIFAR" if INPUT_SHAPES[args.arch][0][1] == 32 else "Synthetic"
     cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
@@ -294,7 +297,7 @@ def _lr_steps(args):
 
 
 def _num_classes(args) -> int:
-    if (args.synthetic or not args.data) and args.arch.startswith("vit"):
+    if (args.synthetic or not args.data) and args.arch.startswith(("vit", "convnext")):
         return 10 if _synthetic_kind(args) == "SyntheticCIFAR" else 1000
     return {"CIFAR10": 10, "SyntheticCIFAR": 10, "CUB200": 200, "Place365": 365}.get(
         args.dataset_type, 10 if (args.synthetic or not args.data) and args.arch.startswith("mobilenet") else 1000)

@@ -46,7 +46,7 @@ class StepConfig:
     clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
     trust_coefficient: float = 1e-3  # optimizer == "lars"
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
-    drop_path_rate: float = 0.0     # ViT only: stochastic depth, linear over the blocks (ops/drop_path.py)
+    drop_path_rate: float = 0.0     # ViT / ConvNeXt: stochastic depth, linear over the blocks (ops/drop_path.py)
     ema_decay: float = 0.0          # weight EMA inside the optimizer's step kernels (ops/optim.py); 0 = off
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
@@ -124,8 +124,9 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
     if cfg.image_size and cfg.model.startswith("vit"):
         kw["image_size"] = cfg.image_size
     if cfg.drop_path_rate:
-        if not cfg.model.startswith("vit"):
-            raise ValueError(f"drop_path_rate is for ViT models only, not {cfg.model}")
+        if not cfg.model.startswith(("vit", "convnext")):
+            raise ValueError(f"--drop-path is for ViT archs only (and convnext_*): drop_path_rate does not apply "
+                             f"to {cfg.model}")
         kw["drop_path_rate"] = cfg.drop_path_rate
     model = build_model(cfg.model, **kw)
     if cfg.checkpoint_segments > 1:

@@ -11,7 +11,7 @@ from __future__ import annotations
 import importlib
 from typing import Dict, Iterable, List
 
-_MODULES = ("attention", "batchnorm", "bn_fold", "conv1x1", "conv_igemm", "depthwise", "fused", "layernorm",
+_MODULES = ("attention", "batchnorm", "bn_fold", "conv1x1", "conv_igemm", "depthwise", "depthwise7", "fused", "layernorm",
             "linear", "loss", "patch_embed", "pool", "stem")
 
 
