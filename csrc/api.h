@@ -289,6 +289,14 @@ void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_av
                      const c10::optional<at::Tensor>& ema, double ema_decay);
 int64_t adamw_grid_cap();  // most blocks adamw_flat_step launches (256 threads, 8 elements each)
 
+// ---- optim/fused_adamw_scaled.hip ----
+void adamw_flat_step_scaled(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg,
+                            at::Tensor& exp_avg_sq, const at::Tensor& grad, at::Tensor& param,
+                            const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper,
+                            const at::Tensor& lr_class, const at::Tensor& lr_scales, double lr, double beta1,
+                            double beta2, double eps, double weight_decay,
+                            const c10::optional<at::Tensor>& ema, double ema_decay);
+
 // ---- optim/fused_lars.hip ----
 void lars_norm_partials(const c10::optional<at::Tensor>& master, const at::Tensor& grad,
                         const at::Tensor& param, const at::Tensor& items, at::Tensor& partials);

@@ -332,6 +332,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0,
         py::call_guard<py::gil_scoped_release>());
   m.def("adamw_grid_cap", &dmp::adamw_grid_cap);
+  m.def("adamw_flat_step_scaled", &dmp::adamw_flat_step_scaled, py::arg("master"), py::arg("exp_avg"),
+        py::arg("exp_avg_sq"), py::arg("grad"), py::arg("param"), py::arg("decay_mask"), py::arg("hyper"),
+        py::arg("lr_class"), py::arg("lr_scales"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0,
+        "adamw_flat_step with lr * lr_scales[lr_class[v]] as the learning rate of 8-element vector v",
+        py::call_guard<py::gil_scoped_release>());
   m.def("lars_norm_partials", &dmp::lars_norm_partials, py::arg("master"), py::arg("grad"), py::arg("param"),
         py::arg("items"), py::arg("partials"),
         "partials[i] = {sum g^2, sum w^2} over work item i (fixed order, no atomics)",

@@ -10,6 +10,7 @@ from .mobilenetv2 import (HeadPool, InvertedResidual, MobileNetV2, mobilenet_v2,
 from .resnet import BasicBlock, Bottleneck, ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
 from .convnext import ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, convnext_test, convnext_tiny
 from .vit import VisionTransformer, vit_b_16, vit_tiny
+from .layer_decay import layer_decay_scales, layer_ids
 
 MODELS: Dict[str, Callable[..., nn.Module]] = {
     "mobilenetv2": mobilenet_v2,
@@ -54,7 +55,17 @@ def build_model(name: str, **kw) -> nn.Module:
         raise ValueError(f"unknown model {name!r}; choose from {sorted(MODELS)}") from None
 
 
-__all__ = ["MODELS", "INPUT_SHAPES", "build_model", "MobileNetV2", "InvertedResidual", "HeadPool",
+def classifier_name(model: nn.Module) -> str:
+    """Name of the model's classifier (its last, class-count-shaped layer): the
+    prefix of the checkpoint entries ``load_weights(reset_head=True)`` may drop."""
+    for cls, name in ((VisionTransformer, "head"), (ConvNeXt, "head"), (ResNet, "fc"), (MobileNetV2, "linear")):
+        if isinstance(model, cls):
+            return name
+    raise ValueError(f"classifier_name: unknown model class {type(model).__name__}")
+
+
+__all__ = ["MODELS", "INPUT_SHAPES", "build_model", "classifier_name", "layer_ids", "layer_decay_scales",
+           "MobileNetV2", "InvertedResidual", "HeadPool",
            "mobilenet_v2", "mobilenet_v2_nobn", "mobilenet_v2_224", "ResNet", "BasicBlock", "Bottleneck", "resnet18",
            "resnet34", "resnet50", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
            "vit_tiny", "ConvNeXt", "ConvNeXtBlock", "convnext_tiny", "convnext_small", "convnext_base",

@@ -34,8 +34,9 @@ without it and a ``lerp_`` pass after it.
 from __future__ import annotations
 
 import contextlib
+import math
 import warnings
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 
@@ -486,6 +487,7 @@ class _SGDRule:
 # hyper[] slots written by adamw_prepare (csrc/optim/fused_adamw.hip)
 _BC1, _BC2, _NORM, _CLIP = range(4)
 _SUMSQ_BLOCKS = 1024  # partial sums per group: 4 blocks per CU of an MI355X
+_LR_CLASSES = 256     # entries of the lr-scale table: one per value of a class byte
 
 
 class _AdamWRule:
@@ -497,6 +499,17 @@ class _AdamWRule:
     never syncs the host, and a step captured into a hipGraph advances them on
     every replay.  ``lr`` is passed as a host scalar (a captured graph bakes
     it, the constant-LR limit of ``--graph``).
+
+    ``lr_scales`` (layer-wise lr decay for fine-tuning) maps parameters to a
+    factor on ``lr``; a parameter not in it gets 1.0.  The update stays one
+    launch per dtype group: every 8-element vector of a flat carries a class
+    byte (``lr_class``, built like the decay mask and rebuilt with the layout)
+    that indexes a 256-entry fp32 table on the device, read by
+    ``adamw_flat_step_scaled`` (``csrc/optim/fused_adamw_scaled.hip``).  A
+    scale of 0 freezes a tensor (its moments still update); with no scales, or
+    all of them 1.0, the step is ``adamw_flat_step`` as before.  The scales are
+    configuration, like ``lr``: they are not in ``state_dict()``, a resumed run
+    passes them again.
     """
 
     KIND = "adamw"
@@ -524,6 +537,90 @@ class _AdamWRule:
             raise ValueError("%s supports one param group (decay is switched per parameter by "
                              "no_decay_1d)" % self._name())
         super().add_param_group(param_group)
+
+    # ------------------------------------------------------------------ #
+    # per-parameter lr scales
+    def _check_lr_scales(self, lr_scales) -> Dict[int, float]:
+        own = {id(p) for grp in self.param_groups for p in grp["params"]}
+        out: Dict[int, float] = {}
+        for p, v in (lr_scales or {}).items():
+            if id(p) not in own:
+                raise ValueError("%s: lr_scales has a key that is not one of the optimizer's parameters"
+                                 % self._name())
+            v = float(v)
+            if not math.isfinite(v) or v < 0.0:
+                raise ValueError("%s: lr scales must be finite and not negative, got %r" % (self._name(), v))
+            out[id(p)] = v
+        values = sorted({out.get(i, 1.0) for i in own})
+        if len(values) > _LR_CLASSES:
+            raise ValueError("%s: %d distinct lr scales, at most %d fit the class byte"
+                             % (self._name(), len(values), _LR_CLASSES))
+        return out
+
+    def _init_lr_scales(self, lr_scales) -> None:
+        self._lr_dev: List[dict] = []  # per group: {"cls": uint8 [numel / 8], "table": fp32 [256]}
+        self._lr_key = None
+        self._lr_by_id = self._check_lr_scales(lr_scales)
+
+    def _lr_values(self) -> List[float]:
+        """The distinct scales, ascending: a parameter's class byte is its scale's index here."""
+        return sorted({self._lr_by_id.get(id(p), 1.0) for grp in self.param_groups for p in grp["params"]})
+
+    @property
+    def lr_scaled(self) -> bool:
+        """Some parameter's scale is not 1.0: ``step()`` runs the scaled kernel."""
+        return any(v != 1.0 for v in self._lr_by_id.values())
+
+    def lr_scale_of(self, p) -> float:
+        return self._lr_by_id.get(id(p), 1.0)
+
+    def lr_scale_range(self) -> Tuple[float, float]:
+        """(min, max) of the scales over the optimizer's parameters (host-side)."""
+        values = self._lr_values()
+        return (values[0], values[-1]) if values else (1.0, 1.0)
+
+    def _lr_host(self, gi: int, numel: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        values = self._lr_values()
+        index = {v: i for i, v in enumerate(values)}
+        cls = torch.zeros(numel // 8, dtype=torch.uint8)
+        for p, off in self._slots(gi):
+            if off % 8:
+                raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
+                                   % (self._name(), off))
+            cls[off // 8:(off + p.numel() + 7) // 8] = index[self.lr_scale_of(p)]  # the slot's padding too
+        # a class no tensor uses poisons what reads it, rather than training it at some other rate
+        table = torch.full((_LR_CLASSES,), float("nan"), dtype=torch.float32)
+        table[:len(values)] = torch.tensor(values, dtype=torch.float64).float()
+        return cls, table
+
+    def _lr_tensors(self, groups: List[dict]) -> List[dict]:
+        """Per group the class bytes and the table on the group's device,
+        rebuilt when the layout changes (a DDP bucket rebuild), as the decay masks are."""
+        key = (self._layout_id(), len(groups))
+        if self._lr_key != key:
+            dev = []
+            for gi, st in enumerate(groups):
+                cls, table = self._lr_host(gi, st["param"].numel())
+                dev.append({"cls": cls.to(st["param"].device), "table": table.to(st["param"].device)})
+            self._lr_dev, self._lr_key = dev, key
+        return self._lr_dev
+
+    @torch.no_grad()
+    def set_lr_scales(self, lr_scales: Optional[Mapping[torch.nn.Parameter, float]]) -> None:
+        """Replace the scales (``None``: all 1.0).  Class bytes and table that are
+        already on the device are rewritten IN PLACE, so a step captured into a
+        hipGraph with scales sees the new ones on its next replay (a step
+        captured without scales runs the unscaled kernel and stays that way)."""
+        self._lr_by_id = self._check_lr_scales(lr_scales)
+        if self._lr_key is None:
+            return
+        groups = self._current_groups()
+        if self._lr_key != (self._layout_id(), len(groups)):
+            return  # stale: the next step rebuilds them
+        for gi, (st, d) in enumerate(zip(groups, self._lr_dev)):
+            cls, table = self._lr_host(gi, st["param"].numel())
+            d["cls"].copy_(cls)
+            d["table"].copy_(table)
 
     # ------------------------------------------------------------------ #
     def _device_state(self, dev: torch.device) -> dict:
@@ -570,6 +667,9 @@ class _AdamWRule:
         if not groups:
             return
         masks = self._decay_masks(groups)
+        # a step that has ever run scaled keeps reading the device tables (a captured one does anyway)
+        scaled = self.lr_scaled or self._lr_key == (self._layout_id(), len(groups))
+        scales = self._lr_tensors(groups) if scaled else [None] * len(groups)
         part = None
         if clip > 0:
             part = self._partials
@@ -588,17 +688,22 @@ class _AdamWRule:
                                                             float(b1), float(b2))
             else:
                 _adamw_prepare_reference(part, ds["hyper"], ds["step"], clip, b1, b2)
-        for st, mask in zip(groups, masks):
+        for st, mask, sc in zip(groups, masks, scales):
             pflat = st["param"]
             hyper = self._dev_state[pflat.device]["hyper"]
-            if pflat.is_cuda:
+            if pflat.is_cuda and sc is not None:
+                _native.require(self._name()).adamw_flat_step_scaled(
+                    st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, mask, hyper,
+                    sc["cls"], sc["table"], float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                    float(g["weight_decay"]), *self._ema_args(st))
+            elif pflat.is_cuda:
                 _native.require(self._name()).adamw_flat_step(
                     st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, mask, hyper,
                     float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
                     *self._ema_args(st))
             else:
                 _adamw_reference(st.get("master"), st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat,
-                                 mask, hyper, g)
+                                 mask, hyper, g, None if sc is None else sc["table"][sc["cls"].long()])
 
     @property
     def last_grad_norm(self) -> Optional[torch.Tensor]:
@@ -788,10 +893,12 @@ class FlatAdamW(_AdamWRule, _DDPLayout, _FlatOptimizer):
     def __init__(self, ddp, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  max_grad_norm: Optional[float] = None, no_decay_1d: bool = True,
                  master_weights: bool = True, amsgrad: bool = False, maximize: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None):
         defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
                                         amsgrad, maximize)
         super().__init__(list(ddp._params), defaults)
+        self._init_lr_scales(lr_scales)
         self._init_layout(ddp, master_weights, ema_decay, ema_warmup)
 
 
@@ -801,7 +908,8 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
     def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None,
                  no_decay_1d: bool = True, master_weights: bool = True, amsgrad: bool = False,
-                 maximize: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                 maximize: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None):
         defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
                                         amsgrad, maximize)
         params = list(params)
@@ -812,6 +920,7 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
             params = list(params[0]["params"])
         params = [p for p in params if p.requires_grad]
         super().__init__(params, defaults)
+        self._init_lr_scales(lr_scales)
         self._init_layout(params, master_weights, ema_decay, ema_warmup)
         self._clip_devices(self._groups)
 
@@ -853,12 +962,16 @@ class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
 def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 0.9,
                     weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                     clip_grad_norm: float = 0.0, trust_coefficient: float = 1e-3,
-                    ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                    ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                    lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None):
     """The trainer's optimizer: ``kind`` sgd | adamw | lars; ``flat`` picks the
     DDP-flat class (``target`` is the DDP wrapper) over the parameter-list one.
-    ``ema_decay`` (``None`` / 0 = off) keeps a weight EMA in the optimizer."""
+    ``ema_decay`` (``None`` / 0 = off) keeps a weight EMA in the optimizer;
+    ``lr_scales`` (adamw only) maps parameters to a factor on ``lr``."""
     if kind in ("sgd", "lars") and clip_grad_norm:
         raise ValueError("gradient clipping needs optimizer='adamw'")
+    if kind in ("sgd", "lars") and lr_scales is not None:
+        raise ValueError("per-parameter lr scales (layer-wise lr decay) need optimizer='adamw'")
     ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if kind == "sgd":
         return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
@@ -866,7 +979,8 @@ def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 
     if kind == "adamw":
         return (FlatAdamW if flat else MasterAdamW)(target, lr=lr, betas=betas, eps=eps,
                                                     weight_decay=weight_decay,
-                                                    max_grad_norm=clip_grad_norm or None, **ema)
+                                                    max_grad_norm=clip_grad_norm or None,
+                                                    lr_scales=lr_scales, **ema)
     if kind == "lars":
         return (FlatLARS if flat else MasterLARS)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
                                                   trust_coefficient=trust_coefficient, eps=eps, **ema)
@@ -949,23 +1063,39 @@ def _adamw_prepare_reference(partials: Optional[torch.Tensor], hyper: torch.Tens
 
 def _adamw_reference(master: Optional[torch.Tensor], exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
                      grad: torch.Tensor, param: torch.Tensor, decay_mask: Optional[torch.Tensor],
-                     hyper: torch.Tensor, g: dict) -> None:
-    """PyTorch implementation of adamw_flat_step, fp32 like the kernel."""
+                     hyper: torch.Tensor, g: dict, scale: Optional[torch.Tensor] = None) -> None:
+    """PyTorch implementation of adamw_flat_step, fp32 like the kernel; with
+    ``scale`` (fp32 [numel / 8], one lr factor per 8-element vector) of
+    adamw_flat_step_scaled: a vector with scale 1 takes the arithmetic of the
+    unscaled call, any other one ``lr * scale`` in fp32, and a vector with
+    scale 0 keeps its weights bit for bit while its moments update."""
     w = master if master is not None else param
     b1, b2 = g["betas"]
     wf = w if w.dtype == torch.float32 else w.float()
     gr = grad.float() * hyper[_CLIP]
     decay = 1.0 - g["lr"] * g["weight_decay"]
+    step = g["lr"] / hyper[_BC1]
+    frozen = None
+    if scale is not None:
+        sv = scale.to(device=wf.device, dtype=torch.float32).repeat_interleave(8)
+        unit, frozen = sv == 1, sv == 0
+        lr_v = torch.tensor(g["lr"], dtype=torch.float32, device=wf.device) * sv
+        decay = torch.where(unit, torch.tensor(decay, dtype=torch.float32, device=wf.device),
+                            1.0 - lr_v * g["weight_decay"])
+        step = torch.where(unit, step, lr_v / hyper[_BC1])
+        w0 = wf.clone()
     if decay_mask is None:
         wf.mul_(decay)
     else:
         keep = decay_mask.repeat_interleave(8) != 0
-        wf.mul_(torch.where(keep, torch.tensor(decay, dtype=torch.float32, device=wf.device),
+        wf.mul_(torch.where(keep, torch.as_tensor(decay, dtype=torch.float32, device=wf.device),
                             torch.ones((), dtype=torch.float32, device=wf.device)))
     exp_avg.mul_(b1).add_(gr, alpha=1 - b1)
     exp_avg_sq.mul_(b2).addcmul_(gr, gr, value=1 - b2)
     denom = (exp_avg_sq.sqrt() / hyper[_BC2].sqrt()).add_(g["eps"])  # sqrt(v) + eps: 0 / eps = 0
-    wf.sub_((g["lr"] / hyper[_BC1]) * (exp_avg / denom))
+    wf.sub_(step * (exp_avg / denom))
+    if frozen is not None:
+        wf.copy_(torch.where(frozen, w0, wf))
     if wf is not w:
         w.copy_(wf.to(w.dtype))
     if master is not None:

@@ -100,6 +100,18 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
                          "are mutually exclusive")
         if args.parallel == "pipe":
             parser.error("--init-from with --parallel pipe is not supported")
+    if args.reset_head and not args.init_from:
+        parser.error("--reset-head needs --init-from")
+    if not 0.0 < args.layer_decay <= 1.0:
+        parser.error("--layer-decay must be in (0, 1]")
+    if args.layer_decay < 1.0:
+        if args.optimizer != "adamw":
+            parser.error("--layer-decay needs --optimizer adamw")
+        if not args.arch.startswith(("vit", "convnext")):
+            parser.error(f"--layer-decay is for ViT (vit_*) and ConvNeXt (convnext_*) archs, not --arch {args.arch}")
+        if args.parallel == "pipe":
+            parser.error("--layer-decay with --parallel pipe is not supported "
+                         "(per-stage optimizers see partial models)")
     if args.augment_staging is not None and not args.gpu_augment:
         parser.error("--augment-staging needs --gpu-augment")
     if args.gpu_augment:
@@ -114,14 +126,14 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
                      "(a pipeline's global norm needs a cross-stage reduction)")
 
 
-def _optimizer(args, target, flat: bool):
+def _optimizer(args, target, flat: bool, lr_scales=None):
     from ..ops.optim import build_optimizer
     trust = TRUST_COEFFICIENT if args.trust_coefficient is None else args.trust_coefficient
     return build_optimizer(args.optimizer, target, flat, lr=args.lr, momentum=args.momentum,
                            weight_decay=args.weight_decay, betas=args.betas, eps=args.eps,
                            clip_grad_norm=args.clip_grad_norm, trust_coefficient=trust,
                            ema_decay=getattr(args, "model_ema_decay", 0.0) or None,
-                           ema_warmup=getattr(args, "model_ema_warmup", False))
+                           ema_warmup=getattr(args, "model_ema_warmup", False), lr_scales=lr_scales)
 
 
 def _optimizer_log(args, opt) -> dict:
@@ -192,6 +204,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "not together with --resume from an existing checkpoint")
     p.add_argument("--init-from-ema", action="store_true",
                    help="--init-from: take CKPT's averaged weights (net_ema, written by a --model-ema-decay run)")
+    p.add_argument("--reset-head", action="store_true",
+                   help="--init-from: a classifier whose shape differs from the model's (another class count) is "
+                        "left at its fresh initialisation instead of being an error")
+    p.add_argument("--layer-decay", default=1.0, type=float, metavar="D",
+                   help="--optimizer adamw, ViT and ConvNeXt archs: layer-wise lr decay for fine-tuning, the head "
+                        "trains at --lr and a layer k below it at lr * D^k, in (0, 1] (1 = off; e.g. 0.75 for "
+                        "ViT-B, 0.65 for smaller ones); not with --parallel pipe")
     p.add_argument("--image-size", default=None, type=int, metavar="N",
                    help="ViT archs only: train at N x N pixels (model, ImageNet transforms and synthetic data)")
     p.add_argument("--arch", default="mobilenetv2")
@@ -327,7 +346,8 @@ def run_data_parallel(args, env) -> None:
     model = build_model(args.arch, num_classes=_num_classes(args), **size_kw)
     if args.init_from:
         from ..utils.checkpoint import load_weights
-        load_weights(args.init_from, model, ema=args.init_from_ema)  # before the cast and the optimizer: masters start from these
+        # before the cast and the optimizer: masters start from these
+        load_weights(args.init_from, model, ema=args.init_from_ema, reset_head=args.reset_head)
     if args.checkpoint_segments > 1:
         from ..utils.checkpointing import enable_activation_checkpointing
         enable_activation_checkpointing(model, args.checkpoint_segments)
@@ -338,12 +358,16 @@ def run_data_parallel(args, env) -> None:
         model = model.to(memory_format=torch.channels_last)
     if dtype != torch.float32:
         cast_model(model, dtype)
+    scales = None
+    if args.layer_decay < 1.0:  # on the bare model: its Parameter objects survive DDP's re-homing onto the flats
+        from ..models.layer_decay import layer_decay_scales
+        scales = layer_decay_scales(model, args.layer_decay)
     if args.parallel == "ddp":
         net = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb, flat_parameters=True)
-        opt = _optimizer(args, net, flat=True)
+        opt = _optimizer(args, net, flat=True, lr_scales=scales)
     else:
         # fp32 master weights for bf16 models: same update as DDP's flat optimizer
-        opt = _optimizer(args, model.parameters(), flat=False)
+        opt = _optimizer(args, model.parameters(), flat=False, lr_scales=scales)
         net = DataParallel(model, graphs=args.dp_graphs) if args.parallel == "dp" else model
     sched = build_schedule(opt, args.epochs, args.warmup_epochs, _lr_steps(args), args.lr_gamma)
     from ..utils.debug import rank0_first
@@ -358,6 +382,13 @@ def run_data_parallel(args, env) -> None:
         start_epoch, best = meta["epoch"] + 1, meta["acc"]
     logger = MetricsLogger(args.log_dir, f"{args.parallel}_{args.arch}", env.rank,
                            text_file=f"{args.parallel}_{args.batch_size}.txt")
+    if scales is not None:  # once, at start-up (host-side values: no device read)
+        lo, hi = opt.lr_scale_range()
+        logger.event("layer_decay", decay=args.layer_decay, distinct_scales=len(set(scales.values())),
+                     lr_scale_min=lo, lr_scale_max=hi)
+        if env.is_main:
+            print(f"layer_decay:{args.layer_decay}  distinct_scales:{len(set(scales.values()))}  "
+                  f"lr_scale_min:{lo}  lr_scale_max:{hi}", flush=True)
 
     def to_dev(x, y):
         x = x.to(dev, dtype, non_blocking=True)

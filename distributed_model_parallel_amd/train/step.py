@@ -48,6 +48,7 @@ class StepConfig:
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
     drop_path_rate: float = 0.0     # ViT / ConvNeXt: stochastic depth, linear over the blocks (ops/drop_path.py)
     ema_decay: float = 0.0          # weight EMA inside the optimizer's step kernels (ops/optim.py); 0 = off
+    layer_decay: float = 1.0        # optimizer == "adamw", ViT / ConvNeXt: layer-wise lr decay (1 = off)
     seed: int = 0
     micro_batches: int = 8          # parallel == "pipe"
     schedule: str = "1f1b"          # parallel == "pipe": naive | gpipe | 1f1b
@@ -84,11 +85,24 @@ def synthetic_batch(cfg: StepConfig, device: torch.device, generator_seed: int =
     return x, y
 
 
-def _optimizer(cfg: StepConfig, target, flat: bool) -> torch.optim.Optimizer:
+def _layer_scales(cfg: StepConfig, model: nn.Module):
+    """The lr_scales of cfg.layer_decay for the BARE model (its Parameter objects
+    survive DDP's re-homing onto the flats); None when the decay is off."""
+    if not 0.0 < cfg.layer_decay <= 1.0:
+        raise ValueError(f"layer_decay must be in (0, 1], got {cfg.layer_decay}")
+    if cfg.layer_decay == 1.0:
+        return None
+    if cfg.optimizer != "adamw":
+        raise ValueError("layer_decay needs optimizer='adamw'")
+    from ..models.layer_decay import layer_decay_scales
+    return layer_decay_scales(model, cfg.layer_decay)
+
+
+def _optimizer(cfg: StepConfig, target, flat: bool, lr_scales=None) -> torch.optim.Optimizer:
     return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
                            weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
                            clip_grad_norm=cfg.clip_grad_norm, trust_coefficient=cfg.trust_coefficient,
-                           ema_decay=cfg.ema_decay or None)
+                           ema_decay=cfg.ema_decay or None, lr_scales=lr_scales)
 
 
 def build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
@@ -139,6 +153,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
         model = model.to(memory_format=torch.channels_last)
     if cfg.dtype != torch.float32:
         cast_model(model, cfg.dtype)
+    scales = _layer_scales(cfg, model)  # on the bare model, before it is wrapped
     ndp = max(1, cfg.dp_devices) if (cfg.parallel == "dp" and device.type == "cuda") else 1
     # DP: the single process feeds batch_size images PER GPU (weak scaling, same
     # per-GPU work as DDP), scattered from device_ids[0]
@@ -148,7 +163,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
         wrapped = DistributedDataParallel(model, bucket_cap_mb=cfg.bucket_cap_mb,
                                           first_bucket_mb=cfg.first_bucket_mb,
                                           flat_parameters=True)
-        opt = _optimizer(cfg, wrapped, flat=True)
+        opt = _optimizer(cfg, wrapped, flat=True, lr_scales=scales)
 
         def step() -> torch.Tensor:
             out = wrapped(x)
@@ -160,7 +175,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
     elif cfg.parallel == "dp":
         from ..parallel.data_parallel import DataParallel
         # fp32 master weights + state, one launch per dtype group (same update as DDP's flat optimizer)
-        opt = _optimizer(cfg, model.parameters(), flat=False)
+        opt = _optimizer(cfg, model.parameters(), flat=False, lr_scales=scales)
         reps = max(1, cfg.dp_replicas)
         wrapped = DataParallel(model, device_ids=[d for d in range(ndp) for _ in range(reps)]
                                if device.type == "cuda" else None, graphs=cfg.dp_graphs)
@@ -174,7 +189,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
             return loss
     else:
         wrapped = model
-        opt = _optimizer(cfg, model.parameters(), flat=False)
+        opt = _optimizer(cfg, model.parameters(), flat=False, lr_scales=scales)
 
         def step() -> torch.Tensor:
             out = model(x)
@@ -200,6 +215,8 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
     from ..comm.rccl import default_communicator
     from ..parallel.pipeline import Pipeline
 
+    if cfg.layer_decay != 1.0:
+        raise ValueError("layer_decay with parallel='pipe' is not supported (per-stage optimizers see partial models)")
     torch.manual_seed(cfg.seed)  # every rank builds the same full model, keeps its stage
     kw = {"num_classes": cfg.num_classes} if cfg.num_classes else {}
     model = build_model(cfg.model, **kw)

@@ -153,7 +153,8 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
     return {"epoch": state.get("epoch", 0), "acc": state.get("acc", 0.0), "extra": state.get("extra", {})}
 
 
-def load_weights(path: str, model: nn.Module, map_location=None, ema: bool = False) -> Dict[str, Any]:
+def load_weights(path: str, model: nn.Module, map_location=None, ema: bool = False,
+                 reset_head: bool = False) -> Dict[str, Any]:
     """Initialise `model` from the weights of a checkpoint (fine-tuning): the
     ``net`` entry only (``ema=True``: the averaged weights, ``net_ema``; an
     error when the file has none) -- no optimizer, scheduler or RNG state, and
@@ -161,7 +162,13 @@ def load_weights(path: str, model: nn.Module, map_location=None, ema: bool = Fal
     of another token count is resized onto the model's patch grid
     (``models.vit.resize_pos_embedding``); any other mismatch raises.  Call it
     before the optimizer is built, so fp32 master weights start from the
-    loaded values."""
+    loaded values.
+
+    ``reset_head=True`` (another class count): checkpoint entries of the
+    classifier (``models.classifier_name``) whose shape differs from the
+    model's are dropped and the model keeps its fresh initialisation there;
+    a classifier of equal shape loads as always, and so does everything else,
+    strictly.  The returned dict then says ``head_reset``: whether it happened."""
     state = _load_weights_only(path, map_location or "cpu")
     if ema:
         if not isinstance(state, dict) or state.get("net_ema") is None:
@@ -178,11 +185,23 @@ def load_weights(path: str, model: nn.Module, map_location=None, ema: bool = Fal
         from ..models.vit import resize_pos_embedding
         sd[pe] = resize_pos_embedding(sd[pe], own[pe].shape[1])
         resized = True
+    head_reset = False
+    if reset_head:
+        from ..models import classifier_name
+        prefix = classifier_name(target) + "."
+        keys = [k for k in sd if k.startswith(prefix) and k in own]
+        if any(sd[k].shape != own[k].shape for k in keys):  # weight and bias go together
+            for k in keys:
+                sd[k] = own[k]  # the model's own (fresh) values: the strict load below still sees every key
+            head_reset = True
     target.load_state_dict(sd, strict=True)  # raises on any remaining shape or key mismatch
     ddp = model if hasattr(model, "reducer") else None
     if ddp is not None and ddp.world_size > 1:
         ddp._sync_module_states()
-    return {"pos_embedding_resized": resized}
+    out = {"pos_embedding_resized": resized}
+    if reset_head:
+        out["head_reset"] = head_reset
+    return out
 
 
 def _load_weights_only(path: str, map_location):
