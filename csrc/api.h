@@ -202,6 +202,12 @@ at::Tensor augment_batch(const at::Tensor& src, const at::Tensor& plan, int64_t 
                          const std::vector<double>& mean, const std::vector<double>& std_, at::ScalarType dtype,
                          bool channels_last, bool no_resize);
 
+// ---- data/rand_augment.hip ----
+at::Tensor crop_bytes(const at::Tensor& src, const at::Tensor& plan, int64_t out_h, int64_t out_w);
+at::Tensor rand_augment_apply(const at::Tensor& u8, const at::Tensor& ops, const at::Tensor& args,
+                              const std::vector<int64_t>& hist_slots, const std::vector<int64_t>& fill,
+                              const at::Tensor& table, at::ScalarType dtype, bool channels_last);
+
 // ---- data/batch_mix.hip ----
 at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, const std::vector<int64_t>& box);
 

@@ -78,6 +78,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mean / std normalisation, cast and layout in one launch; no_resize: every box is out_h x out_w (the crop-only kernel; "
         "other rows come out NaN)",
         py::call_guard<py::gil_scoped_release>());
+  m.def("crop_bytes", &dmp::crop_bytes, py::arg("src"), py::arg("plan"), py::arg("out_h"), py::arg("out_w"),
+        "uint8 [B, Hs, Ws, 3] batch -> uint8 [B, out_h, out_w, 3]: augment_batch's crop / bilinear resize / flip by the "
+        "same plan rows, rounded to bytes (half to even), before the RandAugment chain",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("rand_augment_apply", &dmp::rand_augment_apply, py::arg("u8"), py::arg("ops"), py::arg("args"),
+        py::arg("hist_slots"), py::arg("fill"), py::arg("table"), py::arg("dtype"), py::arg("channels_last") = true,
+        "RandAugment op chain over a uint8 [B, H, W, 3] batch: ops int32 [B, n] (codes of data/rand_augment.py), args "
+        "float64 [B, n, 6], hist_slots[k] != 0 when slot k holds an op that needs the histograms, fill the affine ops' "
+        "colour, table the fp32 [3, 256] normalisation table; one apply pass per slot (a histogram pass before it where "
+        "needed), the last one normalises, casts and lays out -> [B, 3, H, W] bf16 / fp32",
+        py::call_guard<py::gil_scoped_release>());
   m.def("gemm_nt_bnbwd", &dmp::gemm_nt_bnbwd, py::arg("A"), py::arg("B"), py::arg("residual"),
         py::arg("bn_x"), py::arg("bn_y"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("bias"), py::arg("res_map") = std::vector<int64_t>{}, py::arg("a2") = py::none(),

@@ -105,7 +105,9 @@ FEATURES = {
                 "-> the step kernel + a lerp_ pass over the masters",
     "gpu_augment": "crop / resize / flip / normalise / cast / layout of a uint8 batch in one kernel (augment.hip, "
                    "data/gpu_augment.py) -> the PyTorch composition, sample by sample",
-    "dwconv7": "native 7x7 depthwise conv of the ConvNeXt blocks (depthwise7.hip, ops/depthwise7.py) -> F.conv2d (MIOpen)",
+    "rand_augment": "RandAugment's byte crop, histogram and per-slot apply kernels (rand_augment.hip, "
+                    "data/rand_augment.py) -> the PyTorch composition, sample by sample",
+    "dwconv7":"native 7x7 depthwise conv of the ConvNeXt blocks (depthwise7.hip, ops/depthwise7.py) -> F.conv2d (MIOpen)",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",
 }

@@ -107,11 +107,21 @@ def _augment_torch(src: torch.Tensor, plan: np.ndarray, H: int, W: int, mean, st
 
 
 def gpu_augment(src: torch.Tensor, plan, size: Union[int, Tuple[int, int]], mean: Sequence[float],
-                std: Sequence[float], dtype: torch.dtype = torch.bfloat16, channels_last: bool = True) -> torch.Tensor:
+                std: Sequence[float], dtype: torch.dtype = torch.bfloat16, channels_last: bool = True,
+                ops=None, fill=None) -> torch.Tensor:
     """Crop / resize / flip / normalise / cast / lay out the ``uint8`` NHWC batch ``src`` by ``plan``
-    (see the module docstring); ``[B, C, out_h, out_w]`` in ``dtype``."""
+    (see the module docstring); ``[B, C, out_h, out_w]`` in ``dtype``.
+
+    With ``ops = (codes, args)`` of ``rand_augment.RandAugmentPlanner.plan`` (``C == 3`` only) the crop
+    is rounded to bytes, the RandAugment op chain follows and the normalisation table runs last
+    (``data/rand_augment.py``; ``fill``: the affine ops' colour, default from ``mean``)."""
     if src.dim() != 4 or src.dtype != torch.uint8:
         raise ValueError(f"gpu_augment: src must be uint8 [B, Hs, Ws, C], got {src.dtype} {tuple(src.shape)}")
+    if ops is not None:
+        from . import rand_augment as RA
+        if src.shape[3] != 3:
+            raise ValueError(f"gpu_augment: ops (RandAugment) need C == 3, got C = {src.shape[3]}")
+        return RA.rand_augment_bytes(RA.crop_bytes(src, plan, size), ops, mean, std, dtype, channels_last, fill)
     H, W = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
     B, C = src.shape[0], src.shape[3]
     if not 1 <= C <= 4 or len(mean) != C or len(std) != C:

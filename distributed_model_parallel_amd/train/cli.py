@@ -114,6 +114,14 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
                          "(per-stage optimizers see partial models)")
     if args.augment_staging is not None and not args.gpu_augment:
         parser.error("--augment-staging needs --gpu-augment")
+    if args.rand_augment is not None:
+        if not args.gpu_augment:
+            parser.error("--rand-augment needs --gpu-augment")
+        from ..data.rand_augment import parse_rand_augment
+        try:
+            parse_rand_augment(args.rand_augment)
+        except ValueError as e:
+            parser.error(str(e))
     if args.gpu_augment:
         if args.parallel == "pipe":
             parser.error("--gpu-augment with --parallel pipe is not supported "
@@ -234,6 +242,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--gpu-augment, ImageNet-style sets: workers resize the shorter side to S and keep the "
                         "central S x S square, from which the random resized crops are drawn "
                         "(default round(size * 8 / 7): 256 for 224, 439 for 384)")
+    p.add_argument("--rand-augment", default=None, metavar="SPEC",
+                   help="--gpu-augment, training batches: RandAugment after the crop / flip, e.g. rand-m9-mstd0.5-inc1 "
+                        "(keys m, n, mstd, p; inc1 required: the 15 'increasing' ops; data/rand_augment.py); the "
+                        "affine ops fill with the dataset's mean colour")
     p.add_argument("--micro-batches", default=1, type=int)
     p.add_argument("--no-pipe-graphs", action="store_true",
                    help="--parallel pipe on GPU: eager micro-batches instead of captured stage graphs")
@@ -397,7 +409,7 @@ def run_data_parallel(args, env) -> None:
         return x, y.to(dev, non_blocking=True)
 
     to_dev_val = to_dev  # without --gpu-augment validation batches go up as training batches do
-    planner = None
+    planner = rand_planner = None
     if args.gpu_augment:  # the batch goes up as bytes; crop / flip / normalise / cast / layout in one kernel
         from ..data import AugmentPlanner, gpu_augment, transforms as T
         is_cifar, size, source = _augment_geometry(args)
@@ -405,15 +417,21 @@ def run_data_parallel(args, env) -> None:
         planner = AugmentPlanner("pad_crop" if is_cifar else "rrc", size, source, seed=args.seed,
                                  rank=env.rank if args.parallel == "ddp" else 0)
         eval_planner = AugmentPlanner("identity", size, size)
+        if args.rand_augment is not None:  # training batches only
+            from ..data.rand_augment import RandAugmentPlanner, fill_from_mean, parse_rand_augment
+            rand_planner = RandAugmentPlanner(**parse_rand_augment(args.rand_augment), fill=fill_from_mean(mean),
+                                              seed=args.seed, rank=env.rank if args.parallel == "ddp" else 0)
 
-        def augment_to_dev(plans):
+        def augment_to_dev(plans, rand=None):
             def feed(x, y):
+                ops = rand.plan(x.shape[0], size, size) if rand is not None else None
                 x = gpu_augment(x.to(dev, non_blocking=True), plans.plan(x.shape[0]), size, mean, std, dtype=dtype,
-                                channels_last=bool(args.channels_last))
+                                channels_last=bool(args.channels_last), ops=ops,
+                                fill=rand.fill if rand is not None else None)
                 return x, y.to(dev, non_blocking=True)
             return feed
 
-        to_dev, to_dev_val = augment_to_dev(planner), augment_to_dev(eval_planner)
+        to_dev, to_dev_val = augment_to_dev(planner, rand_planner), augment_to_dev(eval_planner)
 
     mixer = None
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
@@ -426,6 +444,8 @@ def run_data_parallel(args, env) -> None:
             sampler.set_epoch(epoch)
         if planner is not None:
             planner.set_epoch(epoch)
+        if rand_planner is not None:
+            rand_planner.set_epoch(epoch)
         if mixer is not None:
             mixer.set_epoch(epoch)
         net.train()
