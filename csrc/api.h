@@ -208,6 +208,10 @@ at::Tensor rand_augment_apply(const at::Tensor& u8, const at::Tensor& ops, const
                               const std::vector<int64_t>& hist_slots, const std::vector<int64_t>& fill,
                               const at::Tensor& table, at::ScalarType dtype, bool channels_last);
 
+// ---- data/random_erase.hip ----
+void random_erase(const at::Tensor& x, const at::Tensor& boxes, const c10::optional<at::Tensor>& fill, bool noise);
+at::Tensor philox_bits(const at::Tensor& counters, const at::Tensor& key);
+
 // ---- data/batch_mix.hip ----
 at::Tensor batch_mix(const at::Tensor& x, const at::Tensor& perm, double lam, const std::vector<int64_t>& box);
 

@@ -89,6 +89,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "colour, table the fp32 [3, 256] normalisation table; one apply pass per slot (a histogram pass before it where "
         "needed), the last one normalises, casts and lays out -> [B, 3, H, W] bf16 / fp32",
         py::call_guard<py::gil_scoped_release>());
+  m.def("random_erase", &dmp::random_erase, py::arg("x"), py::arg("boxes"), py::arg("fill") = py::none(),
+        py::arg("noise") = true,
+        "random erasing in place over a dense [B, C, H, W] bf16 / fp32 batch (channels-last or NCHW, C <= 4): host int32 "
+        "boxes [B, 6] rows (x0, y0, w, h, k0, k1), w == 0: not erased; noise: per-element N(0, 1) from Philox4x32-10 at "
+        "counter (x, y, 0, 0) under the row's key (data/random_erase.py), else host float32 fill [B, C] (or zeros)",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("philox_bits", &dmp::philox_bits, py::arg("counters"), py::arg("key"),
+        "Philox4x32-10 of int32 [n, 4] counters under an int32 [2] key as the device computes it (bit patterns)",
+        py::call_guard<py::gil_scoped_release>());
   m.def("gemm_nt_bnbwd", &dmp::gemm_nt_bnbwd, py::arg("A"), py::arg("B"), py::arg("residual"),
         py::arg("bn_x"), py::arg("bn_y"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("bias"), py::arg("res_map") = std::vector<int64_t>{}, py::arg("a2") = py::none(),

@@ -107,6 +107,8 @@ FEATURES = {
                    "data/gpu_augment.py) -> the PyTorch composition, sample by sample",
     "rand_augment": "RandAugment's byte crop, histogram and per-slot apply kernels (rand_augment.hip, "
                     "data/rand_augment.py) -> the PyTorch composition, sample by sample",
+    "random_erase": "random erasing's in-place kernel with per-pixel Philox noise (random_erase.hip, "
+                    "data/random_erase.py) -> the PyTorch composition, box by box",
     "dwconv7":"native 7x7 depthwise conv of the ConvNeXt blocks (depthwise7.hip, ops/depthwise7.py) -> F.conv2d (MIOpen)",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",

@@ -112,6 +112,15 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
         if args.parallel == "pipe":
             parser.error("--layer-decay with --parallel pipe is not supported "
                          "(per-stage optimizers see partial models)")
+    if not 0.0 <= args.reprob <= 1.0:
+        parser.error("--reprob must be in [0, 1]")
+    if args.remode is not None and not args.reprob:
+        parser.error("--remode needs --reprob")
+    if args.remode is None:
+        args.remode = "pixel"
+    if args.reprob and args.parallel == "pipe":
+        parser.error("--reprob with --parallel pipe is not supported "
+                     "(the pipeline path feeds its stages itself and has no batch-level augmentation)")
     if args.augment_staging is not None and not args.gpu_augment:
         parser.error("--augment-staging needs --gpu-augment")
     if args.rand_augment is not None:
@@ -246,6 +255,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--gpu-augment, training batches: RandAugment after the crop / flip, e.g. rand-m9-mstd0.5-inc1 "
                         "(keys m, n, mstd, p; inc1 required: the 15 'increasing' ops; data/rand_augment.py); the "
                         "affine ops fill with the dataset's mean colour")
+    p.add_argument("--reprob", default=0.0, type=float, metavar="P",
+                   help="random erasing of training batches on the device, after the augmentation and before "
+                        "mixup / CutMix: each sample with probability P gets one box of 2 %% to 1/3 of its area "
+                        "overwritten (data/random_erase.py; 0 = off; with or without --gpu-augment; not with "
+                        "--parallel pipe)")
+    p.add_argument("--remode", default=None, choices=["pixel", "rand", "const"],
+                   help="--reprob: what the box is filled with: N(0, 1) noise per element (pixel, the default), "
+                        "one N(0, 1) value per sample and channel (rand) or zeros (const)")
     p.add_argument("--micro-batches", default=1, type=int)
     p.add_argument("--no-pipe-graphs", action="store_true",
                    help="--parallel pipe on GPU: eager micro-batches instead of captured stage graphs")
@@ -433,6 +450,11 @@ def run_data_parallel(args, env) -> None:
 
         to_dev, to_dev_val = augment_to_dev(planner, rand_planner), augment_to_dev(eval_planner)
 
+    eraser = None
+    if args.reprob > 0:  # training batches only, in place on the normalised batch
+        from ..data import RandomErasePlanner, random_erase_
+        eraser = RandomErasePlanner(args.reprob, args.remode, seed=args.seed,
+                                    rank=env.rank if args.parallel == "ddp" else 0)
     mixer = None
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         from ..ops.mix import BatchMixer
@@ -446,6 +468,8 @@ def run_data_parallel(args, env) -> None:
             planner.set_epoch(epoch)
         if rand_planner is not None:
             rand_planner.set_epoch(epoch)
+        if eraser is not None:
+            eraser.set_epoch(epoch)
         if mixer is not None:
             mixer.set_epoch(epoch)
         net.train()
@@ -458,6 +482,8 @@ def run_data_parallel(args, env) -> None:
                 if batch is None:
                     break
                 x, y = to_dev(*batch)
+                if eraser is not None:
+                    x = random_erase_(x, *eraser.plan(x.shape[0], x.shape[2], x.shape[3]), noise=eraser.noise)
             with timer.region("step"), trace_range("train.step"):
                 y_b, lam = None, 1.0
                 if mixer is not None:
