@@ -298,8 +298,6 @@ void adamw_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& exp_av
                      double beta1, double beta2, double eps, double weight_decay,
                      const c10::optional<at::Tensor>& ema, double ema_decay);
 int64_t adamw_grid_cap();  // most blocks adamw_flat_step launches (256 threads, 8 elements each)
-
-// ---- optim/fused_adamw_scaled.hip ----
 void adamw_flat_step_scaled(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg,
                             at::Tensor& exp_avg_sq, const at::Tensor& grad, at::Tensor& param,
                             const c10::optional<at::Tensor>& decay_mask, const at::Tensor& hyper,
@@ -319,10 +317,9 @@ int64_t lars_chunk_elems();   // most elements of one work item (one block of th
 int64_t lars_fold_threads();  // lanes that fold one tensor's partials in lars_trust
 
 // ---- optim/fused_sgd.hip ----
-void sgd_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& mom,
-                   const at::Tensor& grad, const at::Tensor& param, double lr, double wd,
-                   double momentum, double dampening, bool nesterov, double grad_scale,
-                   bool first_step, const c10::optional<at::Tensor>& ema, double ema_decay);
+void sgd_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
+                   at::Tensor& param, double lr, double wd, double momentum, double dampening, bool nesterov,
+                   double grad_scale, bool first_step, const c10::optional<at::Tensor>& ema, double ema_decay);
 
 // ---- pool/maxpool.hip ----
 std::vector<at::Tensor> maxpool2d_forward(const at::Tensor& x, int64_t k, int64_t s, int64_t p);

@@ -30,12 +30,11 @@
 #include <ATen/hip/HIPContext.h>
 #include "../api.h"
 #include "../common.h"
-#include "ema.h"
+#include "flat_step.h"
 
 namespace dmp {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kVecPerLane = 4;                      // norm kernel: vectors in flight per lane
 constexpr int kChunkVec = kThreads * kVecPerLane;   // 1024 vectors = 8192 elements per work item
 constexpr int kItemCols = 3, kTensorCols = 3, kCoefCols = 4;
@@ -159,8 +158,7 @@ __global__ __launch_bounds__(kThreads) void lars_flat_kernel(float* __restrict__
     const int64_t o = ((int64_t)it.first + i) * 8;
     float g[8], w[8], m[8];
     load8(grad + o, g);
-    if constexpr (MASTER) load8(master + o, w);
-    else load8(reinterpret_cast<const float*>(param) + o, w);
+    load_weights<MASTER>(master, param, o, w);
     load8(mom + o, m);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -169,20 +167,9 @@ __global__ __launch_bounds__(kThreads) void lars_flat_kernel(float* __restrict__
       w[j] = fmaf(-lr, m[j], w[j]);
     }
     store8(mom + o, m);
-    if constexpr (MASTER) store8(master + o, w);
-    store8(param + o, w);
-    if constexpr (EMA) {  // e += (1 - decay) * (w - e) on the fp32 weights just formed
-      float e[8];
-      load8(ema + o, e);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = fmaf(omd, w[j] - e[j], e[j]);
-      store8(ema + o, e);
-    }
+    store_weights<MASTER>(master, param, o, w);
+    ema_update<EMA>(ema, o, w, omd);
   }
-}
-
-void check_flat(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
 }
 
 void check_plan(const at::Tensor& t, const char* name, at::ScalarType dtype, int64_t cols, int dev) {
@@ -192,18 +179,12 @@ void check_plan(const at::Tensor& t, const char* name, at::ScalarType dtype, int
               name, " must be a ", dtype, " [n, ", cols, "] tensor on the parameters' device");
 }
 
-// The fp32 weights the norms and the update read: the master, or the fp32 parameters themselves.
-const float* weights_of(const c10::optional<at::Tensor>& master, const at::Tensor& param, int64_t n) {
-  const bool has_master = master.has_value() && master->defined();
-  TORCH_CHECK(param.scalar_type() == at::kBFloat16 || param.scalar_type() == at::kFloat,
-              "param must be bf16 or fp32");
-  TORCH_CHECK(has_master || param.scalar_type() == at::kFloat, "bf16 parameters need an fp32 master buffer");
-  if (!has_master) return param.data_ptr<float>();
-  check_flat(*master, "master");
-  TORCH_CHECK(master->scalar_type() == at::kFloat && master->numel() == n &&
-                  master->get_device() == param.get_device(),
-              "master must be an fp32 flat of the parameters' size");
-  return master->data_ptr<float>();
+// The common checks, and that a plan's int32 vector indices reach every vector of the flats.
+FlatStep lars_args(const c10::optional<at::Tensor>& master, const at::Tensor& grad, const at::Tensor& param,
+                   const c10::optional<at::Tensor>& ema = c10::nullopt, double ema_decay = 0.0) {
+  const FlatStep fs = flat_step_args(master, grad, param, ema, ema_decay);
+  TORCH_CHECK(fs.n / 8 <= INT32_MAX, "flat buffer too large for a 32-bit vector index");
+  return fs;
 }
 
 }  // namespace
@@ -215,29 +196,21 @@ int64_t lars_fold_threads() { return kWave; }
 // (undefined when `param` is fp32).  items: int32 [I, 3]; partials: fp32 [I, 2].
 void lars_norm_partials(const c10::optional<at::Tensor>& master, const at::Tensor& grad,
                         const at::Tensor& param, const at::Tensor& items, at::Tensor& partials) {
-  check_flat(param, "param");
-  check_flat(grad, "grad");
-  const int64_t n = param.numel();
-  const int dev = param.get_device();
-  TORCH_CHECK(grad.numel() == n && grad.get_device() == dev, "grad / param size or device mismatch");
-  TORCH_CHECK(n % 8 == 0, "flat buffers must be padded to a multiple of 8 elements");
-  TORCH_CHECK(n / 8 <= INT32_MAX, "flat buffer too large for a 32-bit vector index");
-  const bool gb = grad.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(gb || grad.scalar_type() == at::kFloat, "grad must be bf16 or fp32");
-  const float* wp = weights_of(master, param, n);
-  check_plan(items, "items", at::kInt, kItemCols, dev);
-  check_plan(partials, "partials", at::kFloat, 2, dev);
+  const FlatStep fs = lars_args(master, grad, param);
+  check_plan(items, "items", at::kInt, kItemCols, fs.dev);
+  check_plan(partials, "partials", at::kFloat, 2, fs.dev);
   const int64_t nitems = items.size(0);
   TORCH_CHECK(partials.size(0) == nitems, "partials must have one row per work item");
   if (nitems == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
-  if (gb)
+  if (fs.grad_bf16)
     hipLaunchKernelGGL((lars_norm_kernel<__bf16>), dim3((unsigned)nitems), dim3(kThreads), 0, stream,
-                       reinterpret_cast<const __bf16*>(grad.data_ptr()), wp, items.data_ptr<int32_t>(),
-                       partials.data_ptr<float>(), n / 8);
+                       static_cast<const __bf16*>(fs.grad), fs.weights(), items.data_ptr<int32_t>(),
+                       partials.data_ptr<float>(), fs.n / 8);
   else
     hipLaunchKernelGGL((lars_norm_kernel<float>), dim3((unsigned)nitems), dim3(kThreads), 0, stream,
-                       grad.data_ptr<float>(), wp, items.data_ptr<int32_t>(), partials.data_ptr<float>(), n / 8);
+                       static_cast<const float*>(fs.grad), fs.weights(), items.data_ptr<int32_t>(),
+                       partials.data_ptr<float>(), fs.n / 8);
 }
 
 // partials: fp32 [I, 2] of lars_norm_partials; tensors: int32 [T, 3];
@@ -266,45 +239,21 @@ void lars_trust(const at::Tensor& partials, const at::Tensor& tensors, at::Tenso
 void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
                     at::Tensor& param, const at::Tensor& items, const at::Tensor& coef, double lr,
                     double momentum, const c10::optional<at::Tensor>& ema, double ema_decay) {
-  check_flat(param, "param");
-  check_flat(grad, "grad");
-  check_flat(mom, "mom");
-  const int64_t n = param.numel();
-  const int dev = param.get_device();
-  TORCH_CHECK(grad.numel() == n && mom.numel() == n, "grad / momentum / param size mismatch");
-  TORCH_CHECK(grad.get_device() == dev && mom.get_device() == dev, "all buffers must be on one device");
-  TORCH_CHECK(n % 8 == 0, "flat buffers must be padded to a multiple of 8 elements");
-  TORCH_CHECK(n / 8 <= INT32_MAX, "flat buffer too large for a 32-bit vector index");
-  TORCH_CHECK(mom.scalar_type() == at::kFloat, "momentum must be fp32");
-  const bool gb = grad.scalar_type() == at::kBFloat16, pb = param.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(gb || grad.scalar_type() == at::kFloat, "grad must be bf16 or fp32");
-  const bool has_master = master.has_value() && master->defined();
-  weights_of(master, param, n);
-  float* mp = has_master ? master->data_ptr<float>() : nullptr;
-  check_plan(items, "items", at::kInt, kItemCols, dev);
-  check_plan(coef, "coef", at::kFloat, kCoefCols, dev);
-  float* ep = check_ema(ema, ema_decay, master, param);
-  const float omd = (float)(1.0 - ema_decay);  // formed in double, rounded once
+  const FlatStep fs = lars_args(master, grad, param, ema, ema_decay);
+  float* mo = check_flat_state(mom, "mom", fs);
+  check_plan(items, "items", at::kInt, kItemCols, fs.dev);
+  check_plan(coef, "coef", at::kFloat, kCoefCols, fs.dev);
   const int64_t nitems = items.size(0);
   if (nitems == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
-  auto launch = [&](auto gtag, auto ptag) {
-    using G = decltype(gtag);
-    using P = decltype(ptag);
-    const G* gp = reinterpret_cast<const G*>(grad.data_ptr());
-    P* pp = reinterpret_cast<P*>(param.data_ptr());
-    auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)nitems), dim3(kThreads), 0, stream, mp, mom.data_ptr<float>(), gp,
-                         pp, items.data_ptr<int32_t>(), coef.data_ptr<float>(), n / 8, (int)coef.size(0), (float)lr,
-                         (float)momentum, ep, omd);
-    };
-    if (has_master) ep ? go(lars_flat_kernel<G, P, true, true>) : go(lars_flat_kernel<G, P, true, false>);
-    else ep ? go(lars_flat_kernel<G, P, false, true>) : go(lars_flat_kernel<G, P, false, false>);
-  };
-  if (gb && pb) launch(__bf16{}, __bf16{});
-  else if (gb) launch(__bf16{}, float{});
-  else if (pb) launch(float{}, __bf16{});
-  else launch(float{}, float{});
+  dispatch_flat_step(fs, [&](auto g, auto p, auto m, auto e) {
+    using G = decltype(g);
+    using P = decltype(p);
+    hipLaunchKernelGGL((lars_flat_kernel<G, P, decltype(m)::value, decltype(e)::value>), dim3((unsigned)nitems),
+                       dim3(kThreads), 0, stream, fs.master, mo, static_cast<const G*>(fs.grad),
+                       static_cast<P*>(fs.param), items.data_ptr<int32_t>(), coef.data_ptr<float>(), fs.n / 8,
+                       (int)coef.size(0), (float)lr, (float)momentum, fs.ema, fs.omd);
+  });
 }
 
 }  // namespace dmp

@@ -6,7 +6,8 @@ gradient buffers of ``DistributedDataParallel(..., flat_parameters=True)``:
 gradients there are already RCCL-averaged bucket views, parameters are views
 of a flat buffer with the same layout, so the update of all 161 ResNet-50
 tensors is a single vectorised pass (``csrc/optim/fused_sgd.hip``,
-``csrc/optim/fused_adamw.hip``, ``csrc/optim/fused_lars.hip``).
+``csrc/optim/fused_adamw.hip``, ``csrc/optim/fused_lars.hip``, on the shared
+host path and device helpers of ``csrc/optim/flat_step.h``).
 ``MasterSGD`` / ``MasterAdamW`` / ``MasterLARS`` build the same kind of flat
 buffers for any parameter list.  bf16 parameter groups keep an fp32 master copy
 and fp32 optimizer state inside the optimizer; the kernel writes the bf16
@@ -112,6 +113,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if self.ema_warmup:
             return min(self.ema_decay, (1.0 + k) / (10.0 + k))
         return self.ema_decay
+
+    def _aligned_slots(self, gi: int):
+        """``_slots(gi)``, every offset checked to be a multiple of the kernels' 8-element vector."""
+        for p, off in self._slots(gi):
+            if off % 8:
+                raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
+                                   % (self._name(), off))
+            yield p, off
 
     def _ema_args(self, st: dict):
         """(ema, ema_decay) for the group's step kernel: (None, 0.0) where the
@@ -505,7 +514,7 @@ class _AdamWRule:
     launch per dtype group: every 8-element vector of a flat carries a class
     byte (``lr_class``, built like the decay mask and rebuilt with the layout)
     that indexes a 256-entry fp32 table on the device, read by
-    ``adamw_flat_step_scaled`` (``csrc/optim/fused_adamw_scaled.hip``).  A
+    ``adamw_flat_step_scaled`` (``csrc/optim/fused_adamw.hip``).  A
     scale of 0 freezes a tensor (its moments still update); with no scales, or
     all of them 1.0, the step is ``adamw_flat_step`` as before.  The scales are
     configuration, like ``lr``: they are not in ``state_dict()``, a resumed run
@@ -583,10 +592,7 @@ class _AdamWRule:
         values = self._lr_values()
         index = {v: i for i, v in enumerate(values)}
         cls = torch.zeros(numel // 8, dtype=torch.uint8)
-        for p, off in self._slots(gi):
-            if off % 8:
-                raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
-                                   % (self._name(), off))
+        for p, off in self._aligned_slots(gi):
             cls[off // 8:(off + p.numel() + 7) // 8] = index[self.lr_scale_of(p)]  # the slot's padding too
         # a class no tensor uses poisons what reads it, rather than training it at some other rate
         table = torch.full((_LR_CLASSES,), float("nan"), dtype=torch.float32)
@@ -649,10 +655,7 @@ class _AdamWRule:
             masks = []
             for gi, st in enumerate(groups):
                 mask = torch.ones(st["param"].numel() // 8, dtype=torch.uint8)
-                for p, off in self._slots(gi):
-                    if off % 8:
-                        raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
-                                           % (self._name(), off))
+                for p, off in self._aligned_slots(gi):
                     if p.dim() <= 1:  # biases, LayerNorm / BatchNorm weights
                         mask[off // 8:(off + p.numel() + 7) // 8] = 0
                 masks.append(mask.to(st["param"].device))
@@ -787,10 +790,7 @@ class _LARSRule:
             chunk = _native.require(self._name()).lars_chunk_elems() // 8 if dev.type == "cuda" else 1 << 30
             items, tensors, spans = [], [], []
             nitems = 0
-            for t, (p, off) in enumerate(self._slots(gi)):
-                if off % 8:
-                    raise RuntimeError("%s: parameter slot at offset %d is not 8-element aligned"
-                                       % (self._name(), off))
+            for t, (p, off) in enumerate(self._aligned_slots(gi)):
                 nvec = (p.numel() + 7) // 8
                 adapted = not self.exclude_1d or p.dim() > 1
                 first = torch.arange(off // 8, off // 8 + nvec, chunk, dtype=torch.int32)
@@ -850,6 +850,16 @@ class _LARSRule:
 # --------------------------------------------------------------------------- #
 # the six optimizers
 # --------------------------------------------------------------------------- #
+def _trainable_of_one_group(params, name: str, switch: str) -> list:
+    """The trainable parameters of a parameter list, or of a list of exactly one param-group dict."""
+    params = list(params)
+    if params and isinstance(params[0], dict):
+        if len(params) > 1:
+            raise ValueError("%s supports one param group (%s)" % (name, switch))
+        params = list(params[0]["params"])
+    return [p for p in params if p.requires_grad]
+
+
 class FlatSGD(_SGDRule, _DDPLayout, _FlatOptimizer):
     def __init__(self, ddp, lr: float, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, master_weights: bool = True,
@@ -912,13 +922,7 @@ class MasterAdamW(_AdamWRule, _ListLayout, _FlatOptimizer):
                  lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None):
         defaults = self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, no_decay_1d,
                                         amsgrad, maximize)
-        params = list(params)
-        if params and isinstance(params[0], dict):
-            if len(params) > 1:
-                raise ValueError("MasterAdamW supports one param group (decay is switched per "
-                                 "parameter by no_decay_1d)")
-            params = list(params[0]["params"])
-        params = [p for p in params if p.requires_grad]
+        params = _trainable_of_one_group(params, "MasterAdamW", "decay is switched per parameter by no_decay_1d")
         super().__init__(params, defaults)
         self._init_lr_scales(lr_scales)
         self._init_layout(params, master_weights, ema_decay, ema_warmup)
@@ -948,13 +952,8 @@ class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
                  master_weights: bool = True,
                  ema_decay: Optional[float] = None, ema_warmup: bool = False):
         defaults = self._lars_defaults(lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d)
-        params = list(params)
-        if params and isinstance(params[0], dict):
-            if len(params) > 1:
-                raise ValueError("MasterLARS supports one param group (adaptation is switched per "
-                                 "parameter by exclude_1d)")
-            params = list(params[0]["params"])
-        params = [p for p in params if p.requires_grad]
+        params = _trainable_of_one_group(params, "MasterLARS",
+                                         "adaptation is switched per parameter by exclude_1d")
         super().__init__(params, defaults)
         self._init_layout(params, master_weights, ema_decay, ema_warmup)
 

@@ -1,4 +1,4 @@
-"""csrc/optim/fused_adamw_scaled.hip on the MI355X: the flat AdamW update with a
+"""adamw_scaled_kernel (csrc/optim/fused_adamw.hip) on the MI355X: the flat AdamW update with a
 per-tensor lr scale (one class byte per 8-element vector, a 256-entry table)
 against torch.optim.AdamW with one param group per (class, decay); the bits of
 ``adamw_flat_step`` wherever the scale is 1.0; frozen (scale 0) tensors; the

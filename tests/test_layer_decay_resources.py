@@ -1,5 +1,5 @@
-"""csrc/optim/fused_adamw_scaled.hip compiles to the sixteen instantiations the
-host launches, none of which spills."""
+"""adamw_scaled_kernel of csrc/optim/fused_adamw.hip compiles to the sixteen
+instantiations the host launches, none of which spills."""
 import os
 import shutil
 
@@ -15,7 +15,7 @@ def test_scaled_step_kernel_instantiations_build_without_scratch():
     import sys
     sys.path.insert(0, ROOT)
     from tools.kernel_resources import resources
-    ks = [k for k in resources(os.path.join(ROOT, "csrc/optim", "fused_adamw_scaled.hip"))
+    ks = [k for k in resources(os.path.join(ROOT, "csrc/optim", "fused_adamw.hip"))
           if "adamw_scaled_kernel" in k["name"]]
     assert len(ks) == 16, [k["name"] for k in ks]
     assert not any("adamw_flat_kernel" in k["name"] for k in ks)
