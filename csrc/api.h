@@ -126,6 +126,8 @@ at::Tensor dwconv3x3_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t st
                            int64_t W);
 at::Tensor dwconv3x3_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t stride,
                            at::ScalarType out_dtype, const c10::optional<at::Tensor>& out);
+std::map<std::string, int64_t> dwconv3x3_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t stride,
+                                              at::ScalarType dtype);
 
 // ---- conv/depthwise7.hip ----
 at::Tensor dwconv7x7_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias);

@@ -324,6 +324,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv3x3_wgrad", &dmp::dwconv3x3_wgrad, py::arg("dy"), py::arg("x"), py::arg("stride"),
         py::arg("out_dtype"), py::arg("out") = py::none(),
         py::call_guard<py::gil_scoped_release>());
+  m.def("dwconv3x3_plan", &dmp::dwconv3x3_plan, py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"),
+        py::arg("stride"), py::arg("dtype"));
 
   m.def("dwconv7x7_forward", &dmp::dwconv7x7_forward, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(),
         py::call_guard<py::gil_scoped_release>());

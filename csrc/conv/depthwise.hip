@@ -24,28 +24,23 @@
 //     the pixels it visits, the block combines lanes of the same channel vector
 //     in LDS and writes one fp32 partial row; a column-reduce kernel sums the
 //     partials deterministically (no atomics).
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 #include "../api.h"
-#include "../common.h"
 #include "../launch.h"
+#include "dw_common.h"
 
 namespace dmp {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int TW = 4;  // output columns per lane
+constexpr int TW = 4;                // output columns per lane
+constexpr int kWgradBlocks = 1024;   // target block count of the weight gradient (partial rows)
 
 struct Geo {
   int N, H, W, C, OH, OW, stride;
-  int cv;      // channel vectors
-  int tc;      // channel vectors per block row
-  int spp;     // strips per block pass (kThreads / tc)
-  int strips;  // OW / TW (ceil)
+  ChanSplit cs;          // units = channel vectors
+  int strips, passes;    // forward / weight gradient: ceil(OW / TW) strips per output row, grid.x
+  int istrips, ipasses;  // data gradient: ceil(W / TW) strips per input row, grid.x
+  int64_t total;         // N * OH * strips, host only (read by a kernel it shifts the forward's register counts)
 };
-
-template <typename T>
-__device__ __forceinline__ void ldv(const T* p, float (&v)[Vec16<T>::N]) { Vec16<T>::load(p, v); }
 
 // Window loads are issued unconditionally from clamped addresses and the
 // out-of-range ones zeroed afterwards (a select, not a branch): a load under a
@@ -71,8 +66,6 @@ __device__ __forceinline__ void cvt_masked(typename Vec16<T>::raw r, bool ok, fl
   }
 }
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // The lane's VEC channels x 9 taps straight from the [C][9] weight (the
 // module's own [C,1,3,3] tensor, bf16 or fp32): channels c0..c0+VEC-1 are one
 // contiguous run of 9*VEC elements, read as 16-B (or 8-B) vectors and
@@ -80,15 +73,8 @@ __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > h
 // per forward and per data gradient).  The host checks 16-B base alignment.
 template <typename WT, int VEC>
 __device__ __forceinline__ void load_taps(const WT* __restrict__ wc, int c0, float (&wr)[9][VEC]) {
-  constexpr int NE = 9 * VEC, NB = NE * (int)sizeof(WT);
-  using U = typename std::conditional<NB % 16 == 0, uint4, uint2>::type;
-  constexpr int NU = NB / (int)sizeof(U);
-  const U* p = reinterpret_cast<const U*>(wc + (int64_t)c0 * 9);
-  U r[NU];
-#pragma unroll
-  for (int i = 0; i < NU; ++i) r[i] = p[i];
-  WT e[NE];
-  __builtin_memcpy(e, r, NB);
+  WT e[9 * VEC];
+  load_run(wc + (int64_t)c0 * 9, e);
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -111,16 +97,16 @@ __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(const T* __restrict__ 
   if (MOMENTS) zero_moments(zsums, 2 * g.C);
   constexpr int VEC = Vec16<T>::N;
   const int tid = threadIdx.x;
-  const int lc = tid % g.tc, ls = tid / g.tc;
-  const int cvec = blockIdx.y * g.tc + lc;
-  const bool active_c = ls < g.spp && cvec < g.cv;
+  const int lc = tid % g.cs.tc, ls = tid / g.cs.tc;
+  const int cvec = blockIdx.y * g.cs.tc + lc;
+  const bool active_c = ls < g.cs.spp && cvec < g.cs.units;
   const int c0 = cvec * VEC;
   float wr[9][VEC];
   float ms[VEC], mq[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) { ms[j] = 0.f; mq[j] = 0.f; }
   const int64_t total = (int64_t)g.N * g.OH * g.strips;
-  const int64_t sidx = (int64_t)blockIdx.x * g.spp + ls;
+  const int64_t sidx = (int64_t)blockIdx.x * g.cs.spp + ls;
   if (active_c && sidx < total) {
     load_taps<WT, VEC>(wc, c0, wr);
     const int st = (int)(sidx % g.strips);
@@ -179,15 +165,15 @@ __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(const T* __restrict__ 
       lds[1][j * kThreads + tid] = mq[j];
     }
     __syncthreads();
-    const int nout = g.tc * VEC;
+    const int nout = g.cs.tc * VEC;
     for (int o = tid; o < nout; o += kThreads) {
-      const int c_l = o % g.tc, e = o / g.tc;
-      const int cg = (blockIdx.y * g.tc + c_l) * VEC + e;
+      const int c_l = o % g.cs.tc, e = o / g.cs.tc;
+      const int cg = (blockIdx.y * g.cs.tc + c_l) * VEC + e;
       if (cg >= g.C) continue;
       float s = 0.f, q = 0.f;
-      for (int r = 0; r < g.spp; ++r) {
-        s += lds[0][e * kThreads + r * g.tc + c_l];
-        q += lds[1][e * kThreads + r * g.tc + c_l];
+      for (int r = 0; r < g.cs.spp; ++r) {
+        s += lds[0][e * kThreads + r * g.cs.tc + c_l];
+        q += lds[1][e * kThreads + r * g.cs.tc + c_l];
       }
       part[(int64_t)blockIdx.x * g.C + cg] = s;
       part[(int64_t)(gridDim.x + blockIdx.x) * g.C + cg] = q;
@@ -203,21 +189,20 @@ __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(const T* __restrict__ 
 template <typename T, typename WT, int S>
 __global__ __launch_bounds__(kThreads) void dw_dgrad_kernel(const T* __restrict__ dy,
                                                            const WT* __restrict__ wc,
-                                                           T* __restrict__ dx, Geo g,
-                                                           int istrips) {
+                                                           T* __restrict__ dx, Geo g) {
   constexpr int VEC = Vec16<T>::N;
   const int tid = threadIdx.x;
-  const int lc = tid % g.tc, ls = tid / g.tc;
-  const int cvec = blockIdx.y * g.tc + lc;
-  if (ls >= g.spp || cvec >= g.cv) return;
-  const int64_t total = (int64_t)g.N * g.H * istrips;
-  const int64_t sidx = (int64_t)blockIdx.x * g.spp + ls;
+  const int lc = tid % g.cs.tc, ls = tid / g.cs.tc;
+  const int cvec = blockIdx.y * g.cs.tc + lc;
+  if (ls >= g.cs.spp || cvec >= g.cs.units) return;
+  const int64_t total = (int64_t)g.N * g.H * g.istrips;
+  const int64_t sidx = (int64_t)blockIdx.x * g.cs.spp + ls;
   if (sidx >= total) return;
   const int c0 = cvec * VEC;
   float wr[9][VEC];
   load_taps<WT, VEC>(wc, c0, wr);
-  const int st = (int)(sidx % istrips);
-  const int64_t nr = sidx / istrips;
+  const int st = (int)(sidx % g.istrips);
+  const int64_t nr = sidx / g.istrips;
   const int ih = (int)(nr % g.H);
   const int n = (int)(nr / g.H);
   const int iw0 = st * TW;
@@ -275,9 +260,9 @@ __global__ __launch_bounds__(kThreads) void dw_wgrad_kernel(const T* __restrict_
                                                            float* __restrict__ part) {
   constexpr int VEC = Vec16<T>::N;
   const int tid = threadIdx.x;
-  const int lc = tid % g.tc, ls = tid / g.tc;
-  const int cvec = blockIdx.y * g.tc + lc;
-  const bool active = ls < g.spp && cvec < g.cv;
+  const int lc = tid % g.cs.tc, ls = tid / g.cs.tc;
+  const int cvec = blockIdx.y * g.cs.tc + lc;
+  const bool active = ls < g.cs.spp && cvec < g.cs.units;
   const int c0 = cvec * VEC;
   float acc[9][VEC];
 #pragma unroll
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void dw_wgrad_kernel(const T* __restrict_
   const int64_t total = (int64_t)g.N * g.OH * g.strips;
   if (active) {
     for (int k = 0; k < strips_per_lane; ++k) {
-      const int64_t sidx = ((int64_t)blockIdx.x * strips_per_lane + k) * g.spp + ls;
+      const int64_t sidx = ((int64_t)blockIdx.x * strips_per_lane + k) * g.cs.spp + ls;
       if (sidx >= total) break;
       const int st = (int)(sidx % g.strips);
       const int64_t nr = sidx / g.strips;
@@ -334,13 +319,13 @@ __global__ __launch_bounds__(kThreads) void dw_wgrad_kernel(const T* __restrict_
 #pragma unroll
     for (int j = 0; j < VEC; ++j) lds[j * kThreads + tid] = acc[t][j];
     __syncthreads();
-    const int nout = g.tc * VEC;
+    const int nout = g.cs.tc * VEC;
     for (int o = tid; o < nout; o += kThreads) {
-      const int c_l = o % g.tc, e = o / g.tc;
-      const int cg = (blockIdx.y * g.tc + c_l) * VEC + e;
+      const int c_l = o % g.cs.tc, e = o / g.cs.tc;
+      const int cg = (blockIdx.y * g.cs.tc + c_l) * VEC + e;
       if (cg < g.C) {
         float s = 0.f;
-        for (int r = 0; r < g.spp; ++r) s += lds[e * kThreads + r * g.tc + c_l];
+        for (int r = 0; r < g.cs.spp; ++r) s += lds[e * kThreads + r * g.cs.tc + c_l];
         part[(int64_t)blockIdx.x * 9 * g.C + t * g.C + cg] = s;
       }
     }
@@ -348,77 +333,26 @@ __global__ __launch_bounds__(kThreads) void dw_wgrad_kernel(const T* __restrict_
   }
 }
 
-// out[c] = sum_b part[b][c]  (fp64 accumulation, 32 row-groups x 32 columns per block)
-template <typename OT>
-__global__ __launch_bounds__(1024) void column_reduce_kernel(const float* __restrict__ part, int rb,
-                                                             int ncol, int C, OT* __restrict__ out, int acc) {
-  const int cl = threadIdx.x % 32, g = threadIdx.x / 32;
-  const int c = blockIdx.x * 32 + cl;
-  double a = 0.0;
-  if (c < ncol)
-    for (int i = g; i < rb; i += 32) a += (double)part[(int64_t)i * ncol + c];
-  __shared__ double l[1024];
-  l[threadIdx.x] = a;
-  __syncthreads();
-  for (int s = 16; s > 0; s >>= 1) {
-    if (g < s) l[threadIdx.x] += l[threadIdx.x + s * 32];
-    __syncthreads();
-  }
-  if (g == 0 && c < ncol) {  // [C][9] = [C,1,3,3]; acc: add into the existing gradient
-    OT* o = out + (c % C) * 9 + c / C;
-    *o = (OT)(acc ? l[threadIdx.x] + (double)(float)*o : l[threadIdx.x]);
-  }
-}
-
-Geo make_geo(const at::Tensor& x4, int stride, int VEC) {
+Geo make_geo(int64_t N, int64_t C, int64_t H, int64_t W, int64_t stride, at::ScalarType dtype) {
+  TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
+  TORCH_CHECK(dtype == at::kBFloat16 || dtype == at::kFloat, "dwconv3x3: activations must be bf16 or fp32");
+  const int vec = dtype == at::kBFloat16 ? 8 : 4;  // one 16-B channel vector per lane
+  check_sizes(N, C, H, W, vec, "dwconv3x3");
   Geo g;
-  g.N = (int)x4.size(0);
-  g.C = (int)x4.size(1);
-  g.H = (int)x4.size(2);
-  g.W = (int)x4.size(3);
-  g.stride = stride;
-  g.OH = (g.H + 2 - 3) / stride + 1;
-  g.OW = (g.W + 2 - 3) / stride + 1;
-  g.cv = g.C / VEC;
-  g.tc = g.cv < kThreads ? g.cv : kThreads;
-  g.spp = kThreads / g.tc;
+  g.cs = chan_split(C, vec);
+  g.N = (int)N;
+  g.C = (int)C;
+  g.H = (int)H;
+  g.W = (int)W;
+  g.stride = (int)stride;
+  g.OH = (g.H + 2 - 3) / g.stride + 1;
+  g.OW = (g.W + 2 - 3) / g.stride + 1;
   g.strips = (g.OW + TW - 1) / TW;
+  g.istrips = (g.W + TW - 1) / TW;
+  g.total = (int64_t)g.N * g.OH * g.strips;
+  g.passes = block_passes(g.total, g.cs, "dwconv3x3");
+  g.ipasses = block_passes((int64_t)g.N * g.H * g.istrips, g.cs, "dwconv3x3");
   return g;
-}
-
-void check_nhwc(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4, name, " must be a 4-D GPU tensor");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, name,
-              " must be bf16 or fp32");
-  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), name, " must be channels-last");
-  const int vec = t.scalar_type() == at::kBFloat16 ? 8 : 4;
-  TORCH_CHECK(t.size(1) % vec == 0, name, ": channels must be a multiple of ", vec);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
-}
-
-// The weight as the kernels read it: [C][9] contiguous, bf16 or fp32, 16-B
-// aligned -- the module's own tensor when it already is (flat parameter views
-// are padded to 8 elements), else one converted copy.
-at::Tensor taps(const at::Tensor& w) {
-  TORCH_CHECK(w.dim() == 4 && w.size(1) == 1 && w.size(2) == 3 && w.size(3) == 3,
-              "depthwise weight must be [C,1,3,3]");
-  TORCH_CHECK(w.is_cuda(), "depthwise weight must be a GPU tensor");
-  if (w.is_contiguous() && (w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kFloat) &&
-      reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0)
-    return w;
-  return w.to(at::kFloat).contiguous();
-}
-
-template <typename F>
-void dispatch_w(const at::Tensor& w, F&& f) {
-  if (w.scalar_type() == at::kBFloat16) f(__bf16{});
-  else f(float{});
-}
-
-template <typename F>
-void dispatch_t(const at::Tensor& x, F&& f) {
-  if (x.scalar_type() == at::kBFloat16) f(__bf16{});
-  else f(float{});
 }
 
 }  // namespace
@@ -426,41 +360,32 @@ void dispatch_t(const at::Tensor& x, F&& f) {
 // Forward.  Returns (y, moments-or-undefined); moments = fp64 [2C+1] of y.
 std::vector<at::Tensor> dwconv3x3_forward(const at::Tensor& x, const at::Tensor& w, int64_t stride,
                                           bool moments) {
-  check_nhwc(x, "x");
-  TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
-  const int VEC = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  Geo g = make_geo(x, (int)stride, VEC);
+  check_nhwc(x, "x", true);
+  const Geo g = make_geo(x.size(0), x.size(1), x.size(2), x.size(3), stride, x.scalar_type());
   auto y = at::empty({g.N, g.C, g.OH, g.OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const auto wt = taps(w);
-  TORCH_CHECK(wt.size(0) == g.C, "weight channels do not match x");
+  const auto wt = dw_weight(w, g.C, 3);
   auto stream = at::hip::getCurrentHIPStream();
-  const int64_t total = (int64_t)g.N * g.OH * g.strips;
-  const int cchunks = (g.cv + g.tc - 1) / g.tc;
-  dim3 grid((unsigned)((total + g.spp - 1) / g.spp), (unsigned)cchunks);
+  const dim3 grid((unsigned)g.passes, (unsigned)g.cs.cchunks);
   at::Tensor mom, part;
   double* zt = nullptr;
   if (moments) {
-    part = at::empty({2, (int64_t)grid.x, g.C}, x.options().dtype(at::kFloat));
+    part = at::empty({2, (int64_t)g.passes, g.C}, x.options().dtype(at::kFloat));
     mom = at::empty({2 * (int64_t)g.C + 1}, x.options().dtype(at::kDouble));
-    zt = moments_zero_target(mom.data_ptr<double>(), (int)grid.x);
+    zt = moments_zero_target(mom.data_ptr<double>(), g.passes);
   }
-  dispatch_t(x, [&](auto tag) {
+  dispatch_bf16_f32(x.scalar_type(), [&](auto tag) {
     using T = decltype(tag);
-    dispatch_w(wt, [&](auto wtag) {
+    dispatch_bf16_f32(wt.scalar_type(), [&](auto wtag) {
       using WT = decltype(wtag);
       const WT* wp = reinterpret_cast<const WT*>(wt.data_ptr());
-      if (moments)
-        hipLaunchKernelGGL((g.stride == 1 ? dw_fwd_kernel<T, WT, true, 1> : dw_fwd_kernel<T, WT, true, 2>), grid,
-                           dim3(kThreads), 0, stream, reinterpret_cast<const T*>(x.data_ptr()), wp,
-                           reinterpret_cast<T*>(y.data_ptr()), g, part.data_ptr<float>(), zt);
-      else
-        hipLaunchKernelGGL((g.stride == 1 ? dw_fwd_kernel<T, WT, false, 1> : dw_fwd_kernel<T, WT, false, 2>), grid,
-                           dim3(kThreads), 0, stream, reinterpret_cast<const T*>(x.data_ptr()), wp,
-                           reinterpret_cast<T*>(y.data_ptr()), g, nullptr, nullptr);
+      const auto kern = moments ? (g.stride == 1 ? dw_fwd_kernel<T, WT, true, 1> : dw_fwd_kernel<T, WT, true, 2>)
+                                : (g.stride == 1 ? dw_fwd_kernel<T, WT, false, 1> : dw_fwd_kernel<T, WT, false, 2>);
+      hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, stream, reinterpret_cast<const T*>(x.data_ptr()), wp,
+                         reinterpret_cast<T*>(y.data_ptr()), g, moments ? part.data_ptr<float>() : nullptr, zt);
     });
   });
   if (moments) {
-    bn_reduce_partials_launch(part.data_ptr<float>(), (int)grid.x, g.C, mom.data_ptr<double>(),
+    bn_reduce_partials_launch(part.data_ptr<float>(), g.passes, g.C, mom.data_ptr<double>(),
                               (double)g.N * g.OH * g.OW, stream);
   }
   return {y, mom};
@@ -469,68 +394,76 @@ std::vector<at::Tensor> dwconv3x3_forward(const at::Tensor& x, const at::Tensor&
 // Data gradient: dx [N,C,H,W] channels-last.
 at::Tensor dwconv3x3_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t stride, int64_t H,
                            int64_t W) {
-  check_nhwc(dy, "dy");
-  const int VEC = dy.scalar_type() == at::kBFloat16 ? 8 : 4;
-  auto shape_x = at::empty({dy.size(0), dy.size(1), H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  Geo g = make_geo(shape_x, (int)stride, VEC);
+  check_nhwc(dy, "dy", true);
+  const Geo g = make_geo(dy.size(0), dy.size(1), H, W, stride, dy.scalar_type());
   TORCH_CHECK(g.OH == dy.size(2) && g.OW == dy.size(3), "dy shape does not match the input size");
-  const auto wt = taps(w);
-  TORCH_CHECK(wt.size(0) == g.C, "weight channels do not match dy");
+  auto dx = at::empty({g.N, g.C, g.H, g.W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const auto wt = dw_weight(w, g.C, 3);
   auto stream = at::hip::getCurrentHIPStream();
-  const int istrips = (g.W + TW - 1) / TW;
-  const int64_t total = (int64_t)g.N * g.H * istrips;
-  const int cchunks = (g.cv + g.tc - 1) / g.tc;
-  dim3 grid((unsigned)((total + g.spp - 1) / g.spp), (unsigned)cchunks);
-  dispatch_t(dy, [&](auto tag) {
+  const dim3 grid((unsigned)g.ipasses, (unsigned)g.cs.cchunks);
+  dispatch_bf16_f32(dy.scalar_type(), [&](auto tag) {
     using T = decltype(tag);
-    dispatch_w(wt, [&](auto wtag) {
+    dispatch_bf16_f32(wt.scalar_type(), [&](auto wtag) {
       using WT = decltype(wtag);
       hipLaunchKernelGGL((g.stride == 1 ? dw_dgrad_kernel<T, WT, 1> : dw_dgrad_kernel<T, WT, 2>), grid,
                          dim3(kThreads), 0, stream, reinterpret_cast<const T*>(dy.data_ptr()),
-                         reinterpret_cast<const WT*>(wt.data_ptr()), reinterpret_cast<T*>(shape_x.data_ptr()), g,
-                         istrips);
+                         reinterpret_cast<const WT*>(wt.data_ptr()), reinterpret_cast<T*>(dx.data_ptr()), g);
     });
   });
-  return shape_x;
+  return dx;
 }
 
 // Weight gradient: returns [C,1,3,3] in `out_dtype`.
 at::Tensor dwconv3x3_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t stride,
                            at::ScalarType out_dtype, const c10::optional<at::Tensor>& acc_out) {
-  check_nhwc(dy, "dy");
-  check_nhwc(x, "x");
-  const int VEC = x.scalar_type() == at::kBFloat16 ? 8 : 4;
-  Geo g = make_geo(x, (int)stride, VEC);
+  check_nhwc(dy, "dy", true);
+  check_nhwc(x, "x", true);
+  TORCH_CHECK(out_dtype == at::kBFloat16 || out_dtype == at::kFloat, "weight gradient must be bf16 or fp32");
+  const Geo g = make_geo(x.size(0), x.size(1), x.size(2), x.size(3), stride, x.scalar_type());
   TORCH_CHECK(g.OH == dy.size(2) && g.OW == dy.size(3), "dy shape does not match x");
   auto stream = at::hip::getCurrentHIPStream();
-  const int64_t total = (int64_t)g.N * g.OH * g.strips;
-  const int cchunks = (g.cv + g.tc - 1) / g.tc;
-  // ~1024 blocks total, each lane walking several strips
-  const int64_t lanes_needed = (total + g.spp - 1) / g.spp;
-  const int target = std::max(1, 1024 / cchunks);
-  const int spl = (int)std::max<int64_t>(1, (lanes_needed + target - 1) / target);
-  dim3 grid((unsigned)((lanes_needed + spl - 1) / spl), (unsigned)cchunks);
-  auto part = at::empty({(int64_t)grid.x, 9 * (int64_t)g.C}, x.options().dtype(at::kFloat));
-  dispatch_t(x, [&](auto tag) {
+  const WgradSplit s = wgrad_split(g.passes, g.cs.cchunks, kWgradBlocks);
+  auto part = at::empty({(int64_t)s.blocks, 9 * (int64_t)g.C}, x.options().dtype(at::kFloat));
+  dispatch_bf16_f32(x.scalar_type(), [&](auto tag) {
     using T = decltype(tag);
-    hipLaunchKernelGGL((g.stride == 1 ? dw_wgrad_kernel<T, 1> : dw_wgrad_kernel<T, 2>), grid, dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL((g.stride == 1 ? dw_wgrad_kernel<T, 1> : dw_wgrad_kernel<T, 2>),
+                       dim3((unsigned)s.blocks, (unsigned)g.cs.cchunks), dim3(kThreads), 0, stream,
                        reinterpret_cast<const T*>(dy.data_ptr()),
-                       reinterpret_cast<const T*>(x.data_ptr()), g, spl, part.data_ptr<float>());
+                       reinterpret_cast<const T*>(x.data_ptr()), g, s.per_lane, part.data_ptr<float>());
   });
   // reduced straight into [C,1,3,3] in the parameter dtype (no transpose / cast launches)
-  TORCH_CHECK(out_dtype == at::kBFloat16 || out_dtype == at::kFloat, "weight gradient must be bf16 or fp32");
   at::Tensor acc = acc_target(acc_out, 9 * (int64_t)g.C, out_dtype, "dwconv3x3_wgrad");
   TORCH_CHECK(!acc.defined() || acc.is_contiguous(), "dwconv3x3_wgrad: the accumulation target must be [C,1,3,3] contiguous");
   auto out = acc.defined() ? acc : at::empty({(int64_t)g.C, 1, 3, 3}, x.options().dtype(out_dtype));
-  const int ncol = 9 * g.C;
-  if (out_dtype == at::kBFloat16)
-    hipLaunchKernelGGL((column_reduce_kernel<__bf16>), dim3((ncol + 31) / 32), dim3(1024), 0, stream,
-                       part.data_ptr<float>(), (int)grid.x, ncol, g.C, reinterpret_cast<__bf16*>(out.data_ptr()),
-                       (int)acc.defined());
-  else
-    hipLaunchKernelGGL((column_reduce_kernel<float>), dim3((ncol + 31) / 32), dim3(1024), 0, stream,
-                       part.data_ptr<float>(), (int)grid.x, ncol, g.C, out.data_ptr<float>(), (int)acc.defined());
+  dw_colreduce_launch(part, g.C, 9, out, at::Tensor(), acc.defined(), stream);
   return out;
+}
+
+// The host's work split as plain integers (tests place shapes on its edges).
+std::map<std::string, int64_t> dwconv3x3_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t stride,
+                                              at::ScalarType dtype) {
+  const Geo g = make_geo(N, C, H, W, stride, dtype);
+  const WgradSplit s = wgrad_split(g.passes, g.cs.cchunks, kWgradBlocks);
+  std::map<std::string, int64_t> d;
+  d["vec"] = g.C / g.cs.units;
+  d["OH"] = g.OH;
+  d["OW"] = g.OW;
+  d["cv"] = g.cs.units;
+  d["tc"] = g.cs.tc;
+  d["spp"] = g.cs.spp;
+  d["idle"] = kThreads - g.cs.spp * g.cs.tc;  // lanes with tid / tc >= spp
+  d["cchunks"] = g.cs.cchunks;
+  d["last_chunk_lanes"] = g.cs.units - (g.cs.cchunks - 1) * g.cs.tc;
+  d["strips"] = g.strips;
+  d["total"] = g.total;
+  d["passes"] = g.passes;  // forward grid.x = moment partial rows
+  d["dgrad_strips"] = g.istrips;
+  d["dgrad_grid_x"] = g.ipasses;
+  d["spl"] = s.per_lane;  // the weight gradient's strips per lane
+  d["wgrid"] = s.blocks;
+  // lane rows of the weight-gradient grid that find sidx >= total and break
+  d["wgrad_past_total"] = (int64_t)s.blocks * s.per_lane * g.cs.spp - g.total;
+  return d;
 }
 
 }  // namespace dmp

@@ -30,17 +30,12 @@
 //     bias gradient rides along as a 50th row); lanes of one
 //     channel pair combine in LDS, a block writes one fp32 partial row and a
 //     column reduce folds the rows in fp64 in a fixed order (no atomics).
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <map>
-#include <string>
 #include "../api.h"
-#include "../common.h"
+#include "dw_common.h"
 
 namespace dmp {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int TH = 4, TW = 8;       // outputs per lane: rows x columns (forward, data gradient)
 constexpr int THW = 2;              // rows per lane of the weight gradient (its 100 sums leave room for 2 x 8 dy)
 constexpr int K = 7, PAD = 3, KK = K * K;
@@ -52,16 +47,12 @@ using f32x2 = float __attribute__((ext_vector_type(2)));
 
 struct Geo {
   int N, H, W, C;
-  int cp;       // channel pairs
-  int tc;       // channel pairs per block
-  int spp;      // tiles per block pass (kThreads / tc)
-  int cchunks;  // grid.y
-  int th;       // tile height (TH, or THW for the weight gradient)
+  ChanSplit cs;  // units = channel pairs
+  int th;        // tile height (TH, or THW for the weight gradient)
   int tiles_h, tiles_w;
   int64_t tiles;  // N * tiles_h * tiles_w
+  int passes;     // block passes over the tiles: grid.x of the forward / data gradient
 };
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __device__ __forceinline__ f32x2 bf2_to_f32(uint32_t r) {
   f32x2 v;
@@ -86,15 +77,8 @@ __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __buil
 // gradient's rotated kernel).
 template <typename WT, bool FLIP>
 __device__ __forceinline__ void load_taps(const WT* __restrict__ wc, int c0, f32x2 (&wr)[KK]) {
-  constexpr int NE = 2 * KK;
-  using U = typename std::conditional<sizeof(WT) == 2, uint32_t, uint2>::type;
-  constexpr int NU = NE * (int)sizeof(WT) / (int)sizeof(U);
-  const U* p = reinterpret_cast<const U*>(wc + (int64_t)c0 * KK);
-  U r[NU];
-#pragma unroll
-  for (int i = 0; i < NU; ++i) r[i] = p[i];
-  WT e[NE];
-  __builtin_memcpy(e, r, NE * sizeof(WT));
+  WT e[2 * KK];
+  load_run(wc + (int64_t)c0 * KK, e);
 #pragma unroll
   for (int t = 0; t < KK; ++t) {
     const int s = FLIP ? KK - 1 - t : t;
@@ -112,8 +96,8 @@ struct Lane {
 
 __device__ __forceinline__ Lane place(const Geo& g, int64_t tile, int lc, int ls) {
   Lane l;
-  const int cpair = blockIdx.y * g.tc + lc;
-  l.active = ls < g.spp && cpair < g.cp && tile < g.tiles;
+  const int cpair = blockIdx.y * g.cs.tc + lc;
+  l.active = ls < g.cs.spp && cpair < g.cs.units && tile < g.tiles;
   l.c0 = cpair * 2;
   const int tw = (int)(tile % g.tiles_w);
   const int64_t nr = tile / g.tiles_w;
@@ -167,8 +151,8 @@ __global__ __launch_bounds__(kThreads, 2) void dw7_kernel(const uint32_t* __rest
                                                        const void* __restrict__ extra,
                                                        uint32_t* __restrict__ y, Geo g) {
   const int tid = threadIdx.x;
-  const int lc = tid % g.tc, ls = tid / g.tc;
-  const Lane l = place(g, (int64_t)blockIdx.x * g.spp + ls, lc, ls);
+  const int lc = tid % g.cs.tc, ls = tid / g.cs.tc;
+  const Lane l = place(g, (int64_t)blockIdx.x * g.cs.spp + ls, lc, ls);
   if (!l.active) return;
   f32x2 wr[KK];
   load_taps<WT, FLIP>(wc, l.c0, wr);
@@ -265,12 +249,12 @@ __global__ __launch_bounds__(kThreads, 2) void dw7_wgrad_kernel(const uint32_t* 
                                                              int tiles_per_lane,
                                                              float* __restrict__ part) {
   const int tid = threadIdx.x;
-  const int lc = tid % g.tc, ls = tid / g.tc;
+  const int lc = tid % g.cs.tc, ls = tid / g.cs.tc;
   f32x2 acc[kRows];
 #pragma unroll
   for (int t = 0; t < kRows; ++t) acc[t] = f32x2{0.f, 0.f};
   for (int k = 0; k < tiles_per_lane; ++k) {
-    const Lane l = place(g, ((int64_t)blockIdx.x * tiles_per_lane + k) * g.spp + ls, lc, ls);
+    const Lane l = place(g, ((int64_t)blockIdx.x * tiles_per_lane + k) * g.cs.spp + ls, lc, ls);
     if (!l.active) break;
     int cw = l.c0 >> 1;
     const int64_t img = (int64_t)l.n * g.H;
@@ -328,98 +312,34 @@ __global__ __launch_bounds__(kThreads, 2) void dw7_wgrad_kernel(const uint32_t* 
     lds[0][tid] = acc[t].x;
     lds[1][tid] = acc[t].y;
     __syncthreads();
-    const int cpair = blockIdx.y * g.tc + lc;
-    if (ls == 0 && cpair < g.cp) {
-      float s0 = 0.f, s1 = 0.f;
-      for (int r = 0; r < g.spp; ++r) {
-        s0 += lds[0][r * g.tc + lc];
-        s1 += lds[1][r * g.tc + lc];
+    const int cpair = blockIdx.y * g.cs.tc + lc;
+    if (ls == 0 && cpair < g.cs.units) {
+      float s[2] = {0.f, 0.f};
+      for (int r = 0; r < g.cs.spp; ++r) {
+        s[0] += lds[0][r * g.cs.tc + lc];
+        s[1] += lds[1][r * g.cs.tc + lc];
       }
       float2* dst = reinterpret_cast<float2*>(part + ((int64_t)blockIdx.x * kRows + t) * g.C + cpair * 2);
-      *dst = make_float2(s0, s1);
+      *dst = make_float2(s[0], s[1]);
     }
     __syncthreads();
   }
 }
 
-// out: column j = t*C + c of the partials -> dw[c*49 + t] (t < 49) or db[c]
-// (t == 49); fp64 accumulation, 32 row groups x 32 columns per block.
-template <typename OT>
-__global__ __launch_bounds__(1024) void dw7_reduce_kernel(const float* __restrict__ part, int rb, int C,
-                                                          OT* __restrict__ dw, OT* __restrict__ db) {
-  const int ncol = kRows * C;
-  const int cl = threadIdx.x % 32, g = threadIdx.x / 32;
-  const int j = blockIdx.x * 32 + cl;
-  double a = 0.0;
-  if (j < ncol)
-    for (int i = g; i < rb; i += 32) a += (double)part[(int64_t)i * ncol + j];
-  __shared__ double l[1024];
-  l[threadIdx.x] = a;
-  __syncthreads();
-  for (int s = 16; s > 0; s >>= 1) {
-    if (g < s) l[threadIdx.x] += l[threadIdx.x + s * 32];
-    __syncthreads();
-  }
-  if (g == 0 && j < ncol) {
-    const int t = j / C, c = j % C;
-    if (t < KK) dw[c * KK + t] = (OT)l[threadIdx.x];
-    else db[c] = (OT)l[threadIdx.x];
-  }
-}
-
 Geo make_geo(int64_t N, int64_t C, int64_t H, int64_t W, int th) {
-  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && C >= 8 && C % 8 == 0,
-              "dwconv7x7: need N, H, W >= 1 and C a positive multiple of 8");
-  TORCH_CHECK(N * H * W * C < (1LL << 40) && H < (1 << 20) && W * C < (1LL << 31),
-              "dwconv7x7: tensor too large");
+  check_sizes(N, C, H, W, 8, "dwconv7x7");
   Geo g;
+  g.cs = chan_split(C, 2);
   g.N = (int)N;
   g.C = (int)C;
   g.H = (int)H;
   g.W = (int)W;
-  g.cp = g.C / 2;
-  g.tc = g.cp < kThreads ? g.cp : kThreads;
-  g.spp = kThreads / g.tc;
-  g.cchunks = (g.cp + g.tc - 1) / g.tc;
   g.th = th;
   g.tiles_h = (g.H + th - 1) / th;
   g.tiles_w = (g.W + TW - 1) / TW;
   g.tiles = (int64_t)g.N * g.tiles_h * g.tiles_w;
-  TORCH_CHECK((g.tiles + g.spp - 1) / g.spp < (1LL << 31), "dwconv7x7: grid too large");
+  g.passes = block_passes(g.tiles, g.cs, "dwconv7x7");
   return g;
-}
-
-struct WgradSplit {
-  int tiles_per_lane, blocks;
-};
-
-WgradSplit wgrad_split(const Geo& g) {
-  const int64_t passes = (g.tiles + g.spp - 1) / g.spp;  // block passes over all tiles
-  const int target = std::max(1, kWgradBlocks / g.cchunks);
-  WgradSplit s;
-  s.tiles_per_lane = (int)std::max<int64_t>(1, (passes + target - 1) / target);
-  s.blocks = (int)((passes + s.tiles_per_lane - 1) / s.tiles_per_lane);
-  return s;
-}
-
-void check_act(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.scalar_type() == at::kBFloat16, name,
-              " must be a 4-D bf16 GPU tensor");
-  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), name, " must be channels-last");
-  TORCH_CHECK(t.size(1) % 8 == 0, name, ": channels must be a multiple of 8");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
-}
-
-// The weight as the kernels read it: [C][49] contiguous, bf16 or fp32, 16-B
-// aligned -- the module's own tensor when it already is, else one converted copy.
-at::Tensor taps(const at::Tensor& w, int64_t C) {
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == K && w.size(3) == K,
-              "dwconv7x7: weight must be [C,1,7,7]");
-  TORCH_CHECK(w.is_cuda(), "dwconv7x7: weight must be a GPU tensor");
-  if (w.is_contiguous() && (w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kFloat) &&
-      reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0)
-    return w;
-  return w.to(at::kFloat).contiguous();
 }
 
 template <bool FLIP>
@@ -427,23 +347,20 @@ at::Tensor run(const at::Tensor& x, const at::Tensor& w, const void* extra, cons
   const Geo g = make_geo(x.size(0), x.size(1), x.size(2), x.size(3), TH);
   auto y = at::empty_like(x, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((unsigned)((g.tiles + g.spp - 1) / g.spp), (unsigned)g.cchunks);
-  const uint32_t* xp = reinterpret_cast<const uint32_t*>(x.data_ptr());
-  uint32_t* yp = reinterpret_cast<uint32_t*>(y.data_ptr());
-  if (wt.scalar_type() == at::kBFloat16)
-    hipLaunchKernelGGL((dw7_kernel<__bf16, FLIP>), grid, dim3(kThreads), 0, stream, xp,
-                       reinterpret_cast<const __bf16*>(wt.data_ptr()), extra, yp, g);
-  else
-    hipLaunchKernelGGL((dw7_kernel<float, FLIP>), grid, dim3(kThreads), 0, stream, xp, wt.data_ptr<float>(), extra,
-                       yp, g);
+  dispatch_bf16_f32(wt.scalar_type(), [&](auto wtag) {
+    using WT = decltype(wtag);
+    hipLaunchKernelGGL((dw7_kernel<WT, FLIP>), dim3((unsigned)g.passes, (unsigned)g.cs.cchunks), dim3(kThreads), 0,
+                       stream, reinterpret_cast<const uint32_t*>(x.data_ptr()),
+                       reinterpret_cast<const WT*>(wt.data_ptr()), extra, reinterpret_cast<uint32_t*>(y.data_ptr()), g);
+  });
   return y;
 }
 
 }  // namespace
 
 at::Tensor dwconv7x7_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias) {
-  check_act(x, "x");
-  const auto wt = taps(w, x.size(1));
+  check_nhwc(x, "x", false);
+  const auto wt = dw_weight(w, x.size(1), K);
   at::Tensor b;
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->is_cuda() && bias->dim() == 1 && bias->size(0) == x.size(1), "dwconv7x7: bias must be [C]");
@@ -454,11 +371,11 @@ at::Tensor dwconv7x7_forward(const at::Tensor& x, const at::Tensor& w, const c10
 }
 
 at::Tensor dwconv7x7_dgrad(const at::Tensor& dy, const at::Tensor& w, const c10::optional<at::Tensor>& add) {
-  check_act(dy, "dy");
-  const auto wt = taps(w, dy.size(1));
+  check_nhwc(dy, "dy", false);
+  const auto wt = dw_weight(w, dy.size(1), K);
   const void* ap = nullptr;
   if (add.has_value() && add->defined()) {
-    check_act(*add, "add");
+    check_nhwc(*add, "add", false);
     TORCH_CHECK(add->sizes() == dy.sizes(), "dwconv7x7_dgrad: add must have dx's shape");
     ap = add->data_ptr();
   }
@@ -466,49 +383,42 @@ at::Tensor dwconv7x7_dgrad(const at::Tensor& dy, const at::Tensor& w, const c10:
 }
 
 std::vector<at::Tensor> dwconv7x7_wgrad(const at::Tensor& dy, const at::Tensor& x, at::ScalarType w_dtype) {
-  check_act(dy, "dy");
-  check_act(x, "x");
+  check_nhwc(dy, "dy", false);
+  check_nhwc(x, "x", false);
   TORCH_CHECK(dy.sizes() == x.sizes(), "dwconv7x7_wgrad: dy / x shape mismatch");
   TORCH_CHECK(w_dtype == at::kBFloat16 || w_dtype == at::kFloat, "dwconv7x7_wgrad: weight gradient must be bf16 or fp32");
   const Geo g = make_geo(x.size(0), x.size(1), x.size(2), x.size(3), THW);
-  const WgradSplit s = wgrad_split(g);
+  const WgradSplit s = wgrad_split(g.passes, g.cs.cchunks, kWgradBlocks);
   auto stream = at::hip::getCurrentHIPStream();
   auto part = at::empty({(int64_t)s.blocks, (int64_t)kRows * g.C}, x.options().dtype(at::kFloat));
-  hipLaunchKernelGGL(dw7_wgrad_kernel, dim3((unsigned)s.blocks, (unsigned)g.cchunks), dim3(kThreads), 0, stream,
+  hipLaunchKernelGGL(dw7_wgrad_kernel, dim3((unsigned)s.blocks, (unsigned)g.cs.cchunks), dim3(kThreads), 0, stream,
                      reinterpret_cast<const uint32_t*>(dy.data_ptr()), reinterpret_cast<const uint32_t*>(x.data_ptr()),
-                     g, s.tiles_per_lane, part.data_ptr<float>());
+                     g, s.per_lane, part.data_ptr<float>());
   auto dw = at::empty({(int64_t)g.C, 1, K, K}, x.options().dtype(w_dtype));
   auto db = at::empty({(int64_t)g.C}, x.options().dtype(w_dtype));
-  const int ncol = kRows * g.C;
-  if (w_dtype == at::kBFloat16)
-    hipLaunchKernelGGL((dw7_reduce_kernel<__bf16>), dim3((ncol + 31) / 32), dim3(1024), 0, stream,
-                       part.data_ptr<float>(), s.blocks, g.C, reinterpret_cast<__bf16*>(dw.data_ptr()),
-                       reinterpret_cast<__bf16*>(db.data_ptr()));
-  else
-    hipLaunchKernelGGL((dw7_reduce_kernel<float>), dim3((ncol + 31) / 32), dim3(1024), 0, stream,
-                       part.data_ptr<float>(), s.blocks, g.C, dw.data_ptr<float>(), db.data_ptr<float>());
+  dw_colreduce_launch(part, g.C, KK, dw, db, false, stream);
   return {dw, db};
 }
 
 // The host's work split as plain integers (tests place shapes on its edges).
 std::map<std::string, int64_t> dwconv7x7_plan(int64_t N, int64_t C, int64_t H, int64_t W) {
   const Geo g = make_geo(N, C, H, W, TH), gw = make_geo(N, C, H, W, THW);
-  const WgradSplit s = wgrad_split(gw);
+  const WgradSplit s = wgrad_split(gw.passes, gw.cs.cchunks, kWgradBlocks);
   std::map<std::string, int64_t> d;
   d["tile_h"] = TH;
   d["tile_w"] = TW;
   d["threads"] = kThreads;
   d["channels_per_lane"] = 2;
-  d["channels_per_block"] = g.tc * 2;
-  d["tiles_per_block"] = g.spp;
+  d["channels_per_block"] = g.cs.tc * 2;
+  d["tiles_per_block"] = g.cs.spp;
   d["tiles_h"] = g.tiles_h;
   d["tiles_w"] = g.tiles_w;
   d["tiles"] = g.tiles;
-  d["grid_x"] = (g.tiles + g.spp - 1) / g.spp;
-  d["grid_y"] = g.cchunks;
+  d["grid_x"] = g.passes;
+  d["grid_y"] = g.cs.cchunks;
   d["wgrad_tile_h"] = THW;
   d["wgrad_tiles"] = gw.tiles;
-  d["wgrad_tiles_per_lane"] = s.tiles_per_lane;
+  d["wgrad_tiles_per_lane"] = s.per_lane;
   d["wgrad_blocks"] = s.blocks;
   d["wgrad_rows"] = kRows;
   return d;

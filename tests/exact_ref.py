@@ -1,5 +1,5 @@
 """Plain fp64 references for the depthwise and pooling kernels, on whatever
-device the inputs live on, plus the integer geometry of the depthwise host code.
+device the inputs live on.
 
 Two kinds of comparison use them (tests/test_gpu_depthwise_edges.py,
 tests/test_gpu_pool_edges.py):
@@ -74,29 +74,6 @@ def dw_dgrad_abs(dy, w, stride, h, wd):
 
 def dw_wgrad_abs(dy, x, stride):
     return dw_wgrad(dy.double().abs(), x.double().abs(), stride)
-
-
-def dw_split(n, c, h, w, stride, dtype):
-    """The integers the depthwise host code derives (csrc/conv/depthwise.hip
-    make_geo and the weight-gradient work split), recomputed so that a test
-    which exists to reach a branch can assert that it still does."""
-    vec = 8 if dtype == torch.bfloat16 else 4
-    tw = 4
-    g = {"vec": vec, "OH": dw_out(h, stride), "OW": dw_out(w, stride), "cv": c // vec}
-    g["tc"] = min(g["cv"], 256)
-    g["spp"] = 256 // g["tc"]
-    g["idle"] = 256 - g["spp"] * g["tc"]
-    g["strips"] = -(-g["OW"] // tw)
-    g["cchunks"] = -(-g["cv"] // g["tc"])
-    g["last_chunk_lanes"] = g["cv"] - (g["cchunks"] - 1) * g["tc"]
-    g["total"] = n * g["OH"] * g["strips"]
-    g["passes"] = -(-g["total"] // g["spp"])          # forward grid.x = moment partial rows
-    target = max(1, 1024 // g["cchunks"])
-    g["spl"] = max(1, -(-g["passes"] // target))      # strips_per_lane
-    g["wgrid"] = -(-g["passes"] // g["spl"])
-    # lanes of the weight-gradient grid that find sidx >= total and break
-    g["wgrad_past_total"] = g["wgrid"] * g["spl"] * g["spp"] - g["total"]
-    return g
 
 
 # ---------------------------------------------------------------------------

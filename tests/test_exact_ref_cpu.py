@@ -43,25 +43,6 @@ def test_depthwise_refs_are_exact_on_integers():
         assert float(y.abs().max()) <= 81
 
 
-def test_dw_split_reproduces_the_documented_work_splits():
-    bf, f32 = torch.bfloat16, torch.float32
-    g = R.dw_split(32, 96, 64, 64, 1, bf)
-    assert (g["tc"], g["spp"], g["strips"], g["cchunks"], g["passes"], g["spl"]) == (12, 21, 16, 1, 1561, 2)
-    assert g["wgrad_past_total"] > 0
-    assert R.dw_split(4, 96, 32, 32, 1, bf)["passes"] == 49 and R.dw_split(4, 96, 32, 32, 1, bf)["spl"] == 1
-    assert R.dw_split(1, 24, 4, 4, 1, bf)["idle"] == 1
-    g = R.dw_split(1, 960, 4, 4, 1, bf)
-    assert (g["tc"], g["spp"], g["idle"]) == (120, 2, 16)
-    g = R.dw_split(1, 960, 4, 4, 1, f32)
-    assert (g["tc"], g["spp"], g["idle"]) == (240, 1, 16)
-    for c, dt in ((2056, bf), (1028, f32)):
-        g = R.dw_split(1, c, 5, 5, 2, dt)
-        assert (g["cchunks"], g["last_chunk_lanes"]) == (2, 1)
-    assert R.dw_split(3, 960, 16, 48, 1, bf)["passes"] == 288
-    g = R.dw_split(2, 2056, 17, 62, 1, bf)
-    assert (g["cchunks"], g["spl"], g["wgrad_past_total"]) == (2, 2, 0)
-
-
 POOL_GEOS = [((2, 4, 7, 9), 3, 2, 1), ((2, 4, 8, 4), 3, 2, 1), ((1, 4, 3, 5), 3, 2, 0), ((1, 4, 8, 8), 3, 2, 0),
              ((1, 4, 1, 2), 3, 2, 1), ((2, 4, 10, 10), 2, 2, 0), ((1, 4, 11, 13), 3, 1, 1),
              ((2, 4, 8, 8), 5, 3, 2), ((1, 4, 16, 16), 15, 1, 7)]

@@ -12,8 +12,8 @@ Two kinds of input, each with a bound that needs no measurement:
     wgrad            |out - ref64| <= n*U*T, n = N*OH*OW (+ 2^-8*|ref64| for bf16),
     which is what fp32 fused-multiply-add accumulation gives; accumulating in
     bf16 or dropping a boundary column in some strips breaks them.
-A case that exists to reach a branch recomputes the host's work split
-(exact_ref.dw_split) and asserts that the branch is still reached."""
+A case that exists to reach a branch reads the host's own work split
+(``dwconv3x3_plan``) and asserts that the branch is still reached."""
 import pytest
 import torch
 
@@ -124,7 +124,7 @@ def test_idle_lanes(c, dtype, tc, spp, idle, stride):
     C = _native.require("dw")
     torch.manual_seed(1)
     n, h, w = 2, 5, 6
-    g = R.dw_split(n, c, h, w, stride, dtype)
+    g = C.dwconv3x3_plan(n, c, h, w, stride, dtype)
     assert (g["tc"], g["spp"], g["idle"]) == (tc, spp, idle)
     _check_ints(C, n, c, h, w, stride, dtype, moments=True)
     _check_real(C, n, c, h, w, stride, dtype, dtype)
@@ -137,7 +137,7 @@ def test_two_channel_chunks(c, dtype, stride):
     chunk has cvec >= cv.  Forward with moments, dgrad and wgrad."""
     C = _native.require("dw")
     torch.manual_seed(2)
-    g = R.dw_split(1, c, 5, 5, stride, dtype)
+    g = C.dwconv3x3_plan(1, c, 5, 5, stride, dtype)
     assert g["cchunks"] == 2 and g["last_chunk_lanes"] == 1
     _check_ints(C, 1, c, 5, 5, stride, dtype, moments=True)
     _check_real(C, 1, c, 5, 5, stride, dtype, dtype)
@@ -165,7 +165,7 @@ def test_wgrad_several_strips_per_lane_one_chunk():
     C = _native.require("dw")
     torch.manual_seed(3)
     n, c, h, w, stride = 32, 96, 64, 64, 1
-    g = R.dw_split(n, c, h, w, stride, BF16)
+    g = C.dwconv3x3_plan(n, c, h, w, stride, BF16)
     assert g["cchunks"] == 1 and g["passes"] == 1561 and g["spl"] >= 2
     assert g["total"] % g["spp"] != 0 and g["wgrad_past_total"] > g["spp"]
     x = _cl(_ints((n, c, h, w), BF16))
@@ -191,7 +191,7 @@ def test_wgrad_several_strips_per_lane_two_chunks(n, h, w, past):
     C = _native.require("dw")
     torch.manual_seed(4)
     c, stride = 2056, 1
-    g = R.dw_split(n, c, h, w, stride, BF16)
+    g = C.dwconv3x3_plan(n, c, h, w, stride, BF16)
     assert g["cchunks"] == 2 and g["spp"] == 1 and g["spl"] >= 2
     assert g["wgrad_past_total"] == past
     x = _cl(_ints((n, c, h, w), BF16))
@@ -210,7 +210,7 @@ def test_forward_moments_integers(c, dtype, stride):
     C = _native.require("dw")
     torch.manual_seed(5)
     n, h, w = 4, 11, 26
-    g = R.dw_split(n, c, h, w, stride, dtype)
+    g = C.dwconv3x3_plan(n, c, h, w, stride, dtype)
     assert g["OW"] % 4 != 0 and g["total"] > g["spp"] and g["passes"] >= 2
     _check_ints(C, n, c, h, w, stride, dtype, moments=True)
 
@@ -224,7 +224,7 @@ def test_forward_moments_more_than_256_partial_rows():
     C = _native.require("dw")
     torch.manual_seed(6)
     n, c, h, w, stride = 3, 960, 16, 48, 1
-    g = R.dw_split(n, c, h, w, stride, BF16)
+    g = C.dwconv3x3_plan(n, c, h, w, stride, BF16)
     rows = g["passes"]
     assert rows == 288 and rows > 256 and 4 * g["spp"] <= rows
     x = _cl(_ints((n, c, h, w), BF16))
@@ -258,3 +258,37 @@ def test_real_data_within_fp32_fma_bounds(n, c, h, w, stride, dtype, wdtype):
     C = _native.require("dw")
     torch.manual_seed(7)
     _check_real(C, n, c, h, w, stride, dtype, wdtype)
+
+
+def test_plan_reports_the_documented_work_splits():
+    """The host's own integers (``dwconv3x3_plan`` reads the structs the launches
+    read; it launches nothing) at the splits the cases above are placed on."""
+    C = _native.require("dw")
+    plan = C.dwconv3x3_plan
+    g = plan(32, 96, 64, 64, 1, BF16)
+    assert (g["tc"], g["spp"], g["strips"], g["cchunks"], g["passes"], g["spl"]) == (12, 21, 16, 1, 1561, 2)
+    assert g["wgrad_past_total"] > 0
+    assert plan(4, 96, 32, 32, 1, BF16)["passes"] == 49 and plan(4, 96, 32, 32, 1, BF16)["spl"] == 1
+    assert plan(1, 24, 4, 4, 1, BF16)["idle"] == 1
+    g = plan(1, 960, 4, 4, 1, BF16)
+    assert (g["tc"], g["spp"], g["idle"]) == (120, 2, 16)
+    g = plan(1, 960, 4, 4, 1, F32)
+    assert (g["tc"], g["spp"], g["idle"]) == (240, 1, 16)
+    for c, dt in ((2056, BF16), (1028, F32)):
+        g = plan(1, c, 5, 5, 2, dt)
+        assert (g["cchunks"], g["last_chunk_lanes"]) == (2, 1)
+    assert plan(3, 960, 16, 48, 1, BF16)["passes"] == 288
+    g = plan(2, 2056, 17, 62, 1, BF16)
+    assert (g["cchunks"], g["spl"], g["wgrad_past_total"]) == (2, 2, 0)
+    # the data gradient walks input rows: 62 columns are 16 strips of 4, 2 * 17 * 16 rows of them
+    assert (g["vec"], g["cv"], g["dgrad_strips"], g["dgrad_grid_x"]) == (8, 257, 16, 544)
+
+
+def test_plans_refuse_tensors_beyond_the_index_range():
+    """N*H*W*C = 2^47 elements: past what the kernels' offsets are checked for.
+    Host-only, nothing is allocated."""
+    C = _native.require("dw")
+    with pytest.raises(RuntimeError, match="too large"):
+        C.dwconv3x3_plan(1 << 20, 8, 4096, 4096, 1, BF16)
+    with pytest.raises(RuntimeError, match="too large"):
+        C.dwconv7x7_plan(1 << 20, 8, 4096, 4096)
