@@ -66,6 +66,7 @@ std::vector<at::Tensor> bn_backward_apply(const at::Tensor& dy, const at::Tensor
                                           const c10::optional<at::Tensor>& acc_weight,
                                           const c10::optional<at::Tensor>& acc_bias);
 void set_bn_streaming(bool on);
+std::map<std::string, int64_t> bn_plan(int64_t M, int64_t C, at::ScalarType dtype);
 
 // ---- bn/bn_apply_gram.hip ----
 bool bn_apply_gram_supported(int64_t C);

@@ -197,6 +197,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("set_bn_streaming", &dmp::set_bn_streaming, py::arg("on"),
         "A/B: non-temporal streaming in the BN apply passes over > 256 MB tensors (default on)");
+  m.def("bn_plan", &dmp::bn_plan, py::arg("M"), py::arg("C"), py::arg("dtype"),
+        "the BN kernels' work split for an [M, C] tensor as plain integers (host only)");
   m.def("set_pool_generic", &dmp::set_pool_generic, py::arg("on"),
         "A/B: route every max-pool geometry through the runtime-k kernels (default off)");
   m.def("set_tn_xl_rounds", &dmp::set_tn_xl_rounds, py::arg("rounds"));

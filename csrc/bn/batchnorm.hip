@@ -556,7 +556,8 @@ void check_input(const at::Tensor& x, int64_t C, const char* name) {
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
 }
 
-int vec_of(const at::Tensor& x) { return x.scalar_type() == at::kBFloat16 ? 8 : 4; }
+int vec_of(at::ScalarType t) { return t == at::kBFloat16 ? 8 : 4; }
+int vec_of(const at::Tensor& x) { return vec_of(x.scalar_type()); }
 
 template <typename F>
 void dispatch_t(const at::Tensor& x, F&& f) {
@@ -579,10 +580,14 @@ float* fptr(const c10::optional<at::Tensor>& t) {
 // The apply passes' streaming policy, for bn_apply_gram.hip.
 bool bn_streaming(int64_t M, int64_t C) { return streaming(M, C); }
 
+namespace {
+int reduce_chunks(int rb) { return (rb + kRedRows - 1) / kRedRows; }  // > 1: producer zeroed sums
+}  // namespace
+
 // Shared with the GEMM moments epilogue (csrc/conv/gemm_bf16.hip).
 void bn_reduce_partials_launch(const float* part, int rb, int C, double* sums, double count,
                                hipStream_t stream) {
-  const int chunks = (rb + kRedRows - 1) / kRedRows;  // > 1: producer zeroed sums
+  const int chunks = reduce_chunks(rb);
   hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3((C + kRedCh - 1) / kRedCh, chunks), dim3(1024),
                      0, stream, part, rb, C, sums, count);
 }
@@ -839,5 +844,32 @@ std::vector<at::Tensor> bn_backward_apply(const at::Tensor& dy, const at::Tensor
 }
 
 void set_bn_streaming(bool on) { g_bn_streaming = on; }
+
+// The host's work split for an [M, C] tensor as plain integers, from the code
+// the launches above read (tests place shapes on its edges).  Launches nothing.
+std::map<std::string, int64_t> bn_plan(int64_t M, int64_t C, at::ScalarType dtype) {
+  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16, "bn_plan: float32 or bfloat16");
+  const int vec = vec_of(dtype);
+  TORCH_CHECK(M >= 1 && C >= vec && C % vec == 0, "bn_plan: M >= 1 and channels a multiple of ", vec);
+  const Layout L = make_layout((int)C, vec);
+  const Grid g = plan(M, (int)C, vec);
+  const int64_t rb = g.grid.x;
+  double target;
+  std::map<std::string, int64_t> d;
+  d["vec"] = vec;
+  d["cv"] = L.cv;
+  d["tc"] = L.tc;
+  d["rpi"] = L.rpi;
+  d["idle"] = kThreads - L.tc * L.rpi;  // lanes with tid / tc >= rpi
+  d["cchunks"] = g.grid.y;
+  d["last_chunk_lanes"] = L.cv - ((int64_t)g.grid.y - 1) * L.tc;
+  d["row_blocks"] = rb;  // grid.x = partial rows of a moments launch
+  d["rows_per_block"] = g.rows_per_block;
+  d["last_block_rows"] = M - (rb - 1) * g.rows_per_block;
+  d["reduce_chunks"] = reduce_chunks((int)rb);
+  d["zeroed"] = moments_zero_target(&target, (int)rb) != nullptr;  // the producer zeroes the sums
+  d["streaming"] = streaming(M, C);
+  return d;
+}
 
 }  // namespace dmp

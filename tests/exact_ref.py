@@ -1,8 +1,8 @@
-"""Plain fp64 references for the depthwise and pooling kernels, on whatever
-device the inputs live on.
+"""Plain fp64 references for the depthwise, pooling and batch-norm kernels, on
+whatever device the inputs live on.
 
 Two kinds of comparison use them (tests/test_gpu_depthwise_edges.py,
-tests/test_gpu_pool_edges.py):
+tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py):
   * integer-valued inputs, where every fp32 partial sum is an integer below
     2^24 and every bf16 output an integer of magnitude at most 256: the kernel
     must then equal the fp64 reference bit for bit;
@@ -141,3 +141,127 @@ def bn_pool_backward(dy, taps, x, scale, shift, mean, k, s, p):
     on = x64 * scale.double().view(1, c, 1, 1) + shift.double().view(1, c, 1, 1) > 0
     dz = torch.where(on, g, torch.zeros_like(g))
     return dz, dz.sum(dim=(0, 2, 3)), (dz * (x64 - mean.double().view(1, c, 1, 1))).sum(dim=(0, 2, 3))
+
+
+# ---------------------------------------------------------------------------
+# batch normalisation over the rows of an [M, C] matrix, split into the phases
+# csrc/bn/batchnorm.hip has: moments -> coefficients -> apply, and the same
+# for the backward.  Everything is fp64 and nothing is rounded on the way, so
+# a caller that wants exact equality chooses inputs whose results fp32 holds.
+# ---------------------------------------------------------------------------
+def bn_moments(x):
+    """fp64 [2C+1] = (column sums, column sums of squares, rows)."""
+    xd = x.double()
+    return torch.cat([xd.sum(0), (xd * xd).sum(0), xd.new_tensor([float(x.shape[0])])])
+
+
+def bn_moments_abs(x):
+    """(sum |x|, sum x^2) per channel: what the moments' rounding errors scale with."""
+    xd = x.double()
+    return xd.abs().sum(0), (xd * xd).sum(0)
+
+
+def _or_const(t, like, value):
+    return t.double() if t is not None else torch.full_like(like, value)
+
+
+def bn_fwd_coeffs(sums, weight, bias, eps):
+    """(mean, var, invstd, scale, shift), each fp64 [C], with the arithmetic of
+    csrc/bn/bn_coeffs.h: biased variance clamped at 0, eps as fp32 holds it."""
+    c = (sums.numel() - 1) // 2
+    sums = sums.double()
+    n = sums[2 * c]
+    mean = sums[:c] / n
+    var = (sums[c:2 * c] / n - mean * mean).clamp_min(0.0)
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    invstd = 1.0 / torch.sqrt(var + eps32)
+    scale = _or_const(weight, invstd, 1.0) * invstd
+    shift = _or_const(bias, invstd, 0.0) - mean * scale
+    return mean, var, invstd, scale, shift
+
+
+def bn_eval_coeffs(running_mean, running_var, weight, bias, eps):
+    """(mean, invstd, scale, shift) of an eval-mode BN, from the running statistics."""
+    mean = running_mean.double()
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    invstd = 1.0 / torch.sqrt(running_var.double() + eps32)
+    scale = _or_const(weight, invstd, 1.0) * invstd
+    return mean, invstd, scale, _or_const(bias, invstd, 0.0) - mean * scale
+
+
+def bn_preact(x, scale, shift, residual=None):
+    t = x.double() * scale + shift
+    return t if residual is None else t + residual.double()
+
+
+def bn_apply(x, scale, shift, residual=None, relu=False, clip=float("inf")):
+    """act(x * scale + shift [+ residual]); act = ReLU clipped at `clip` when relu."""
+    t = bn_preact(x, scale, shift, residual)
+    return t.clamp(0.0, clip) if relu else t
+
+
+def bn_apply_abs(x, mean, scale, bias, residual=None):
+    """|x*scale| + |mean*scale| + |bias| + |residual|: the terms the apply rounds."""
+    t = (x.double() * scale).abs() + (mean * scale).abs() + _or_const(bias, scale, 0.0).abs()
+    return t if residual is None else t + residual.double().abs()
+
+
+def bn_running_update(running_mean, running_var, mean, var, n, momentum):
+    """The running statistics after one training step over n rows (unbiased variance)."""
+    n = float(n)
+    unbiased = var * n / (n - 1.0) if n > 1.0 else var
+    return ((1.0 - momentum) * running_mean.double() + momentum * mean,
+            (1.0 - momentum) * running_var.double() + momentum * unbiased)
+
+
+def bn_mask_from_y(y, clip=float("inf")):
+    """Where the clipped ReLU passes a gradient, from its output: 0 < y < clip, both strict."""
+    yd = y.double()
+    return (yd > 0.0) & (yd < clip)
+
+
+def bn_mask_from_x(x, scale, shift, clip=float("inf")):
+    """The same mask re-derived from the BN input (no residual was added)."""
+    return bn_mask_from_y(bn_preact(x, scale, shift), clip)
+
+
+def _dz(dy, mask):
+    dz = dy.double()
+    return dz if mask is None else dz * mask
+
+
+def bn_bwd_moments(dy, x, mean, mask=None):
+    """fp64 [2C] = (sum dz, sum dz*(x - mean)), dz = dy where `mask` (None: everywhere)."""
+    dz = _dz(dy, mask)
+    return torch.cat([dz.sum(0), (dz * (x.double() - mean.double())).sum(0)])
+
+
+def bn_bwd_moments_abs(dy, x, mean, mask=None):
+    dz = _dz(dy, mask).abs()
+    return dz.sum(0), (dz * (x.double() - mean.double()).abs()).sum(0)
+
+
+def bn_bwd_coeffs(sums, count, weight, mean, invstd, training=True):
+    """(a, b, c, dweight, dbias), fp64 [C]: dx = a*dz + b*x + c.  `count` is the
+    global row count; eval mode has b = c = 0."""
+    c_ = sums.numel() // 2
+    sums = sums.double()
+    sdz, sdzx = sums[:c_], sums[c_:]
+    istd = invstd.double()
+    a = _or_const(weight, istd, 1.0) * istd
+    if training:
+        b = -a * istd * istd * sdzx / float(count)
+        c = -a * sdz / float(count) - b * mean.double()
+    else:
+        b, c = torch.zeros_like(a), torch.zeros_like(a)
+    return a, b, c, sdzx * istd, sdz
+
+
+def bn_bwd_apply(dy, x, a, b, c, mask=None):
+    """(dx, dz): dz is also the gradient of a fused residual."""
+    dz = _dz(dy, mask)
+    return a * dz + b * x.double() + c, dz
+
+
+def bn_bwd_apply_abs(dy, x, a, b, c, mask=None):
+    return (a * _dz(dy, mask)).abs() + (b * x.double()).abs() + c.abs()

@@ -80,6 +80,120 @@ def test_pool_forward_tap_formula_by_hand():
     assert taps[0, :, :, 0].tolist() == [[4, 3], [1, 5]]
 
 
+def _bn_case(m, c, seed=0):
+    """Non-degenerate fp64 data: channel means and spreads differ, nothing sits on a ReLU threshold."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(m, c, dtype=torch.float64, generator=g) * (0.5 + torch.rand(c, dtype=torch.float64, generator=g)) \
+        + torch.randn(c, dtype=torch.float64, generator=g) * 2
+    w = torch.randn(c, dtype=torch.float64, generator=g)
+    b = torch.randn(c, dtype=torch.float64, generator=g)
+    res = torch.randn(m, c, dtype=torch.float64, generator=g)
+    dy = torch.randn(m, c, dtype=torch.float64, generator=g)
+    return x, w, b, res, dy
+
+
+@pytest.mark.parametrize("affine", ["both", "no_weight", "no_bias", "neither"])
+@pytest.mark.parametrize("act", [None, "relu", "relu6"])
+@pytest.mark.parametrize("residual", [False, True])
+@pytest.mark.parametrize("m,c", [(2, 4), (37, 8), (200, 24)])
+def test_bn_training_refs_match_batch_norm_autograd(m, c, residual, act, affine):
+    x, w, b, res, dy = _bn_case(m, c)
+    if act == "relu6":
+        x = x * 3  # enough pre-activations above the clip
+    w = w if affine in ("both", "no_bias") else None
+    b = b if affine in ("both", "no_weight") else None
+    eps, momentum = 1e-5, 0.3
+    clip = {None: float("inf"), "relu": float("inf"), "relu6": 6.0}[act]
+    rm0, rv0 = torch.randn(c, dtype=torch.float64), torch.rand(c, dtype=torch.float64) + 0.5
+    leaves = [t.clone().requires_grad_() for t in (x, res) + tuple(t for t in (w, b) if t is not None)]
+    xl, rl = leaves[0], leaves[1]
+    wl = leaves[2] if w is not None else None
+    bl = leaves[-1] if b is not None else None
+    rm, rv = rm0.clone(), rv0.clone()
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    t = F.batch_norm(xl, rm, rv, wl, bl, True, momentum, eps32)
+    if residual:
+        t = t + rl
+    y = t if act is None else F.hardtanh(t, 0.0, clip) if act == "relu6" else F.relu(t)
+    y.backward(dy)
+
+    sums = R.bn_moments(x)
+    assert sums.shape == (2 * c + 1,) and sums[2 * c].item() == m
+    mean, var, invstd, scale, shift = R.bn_fwd_coeffs(sums, w, b, eps)
+    close = dict(atol=1e-11, rtol=1e-11)
+    torch.testing.assert_close(mean, x.mean(0), **close)
+    torch.testing.assert_close(var, x.var(0, unbiased=False), **close)
+    yr = R.bn_apply(x, scale, shift, res if residual else None, act is not None, clip)
+    torch.testing.assert_close(yr, y.detach(), **close)
+    nrm, nrv = R.bn_running_update(rm0, rv0, mean, var, m, momentum)
+    torch.testing.assert_close(nrm, rm, **close)
+    torch.testing.assert_close(nrv, rv, **close)
+
+    mask = None if act is None else R.bn_mask_from_y(yr, clip)
+    if act is not None and not residual:  # both ways to the mask agree off the thresholds
+        assert torch.equal(mask, R.bn_mask_from_x(x, scale, shift, clip))
+        assert 0 < int(mask.sum()) < mask.numel()
+    bs = R.bn_bwd_moments(dy, x, mean, mask)
+    a, bb, cc, dw, db = R.bn_bwd_coeffs(bs, m, w, mean, invstd, True)
+    dx, dz = R.bn_bwd_apply(dy, x, a, bb, cc, mask)
+    torch.testing.assert_close(dx, xl.grad, **close)
+    if residual:
+        torch.testing.assert_close(dz, rl.grad, **close)
+    if w is not None:
+        torch.testing.assert_close(dw, wl.grad, **close)
+    if b is not None:
+        torch.testing.assert_close(db, bl.grad, **close)
+    # the |.|-companions bound what they accompany
+    sa, qa = R.bn_moments_abs(x)
+    assert bool((sa >= sums[:c].abs() - 1e-12).all()) and torch.equal(qa, sums[c:2 * c])
+    ba, bq = R.bn_bwd_moments_abs(dy, x, mean, mask)
+    assert bool((ba >= bs[:c].abs() - 1e-12).all()) and bool((bq >= bs[c:].abs() - 1e-12).all())
+    ya = R.bn_apply_abs(x, mean, scale, b, res if residual else None)
+    assert bool((ya >= R.bn_preact(x, scale, shift, res if residual else None).abs() - 1e-12).all())
+    assert bool((R.bn_bwd_apply_abs(dy, x, a, bb, cc, mask) >= dx.abs() - 1e-12).all())
+
+
+@pytest.mark.parametrize("act", [None, "relu6"])
+def test_bn_eval_refs_match_batch_norm_autograd(act):
+    m, c = 37, 8
+    x, w, b, res, dy = _bn_case(m, c, seed=1)
+    eps = 1e-3
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    clip = 6.0 if act else float("inf")
+    rm, rv = torch.randn(c, dtype=torch.float64), torch.rand(c, dtype=torch.float64) + 0.5
+    xl, wl, bl = (t.clone().requires_grad_() for t in (x, w, b))
+    t = F.batch_norm(xl, rm.clone(), rv.clone(), wl, bl, False, 0.1, eps32)
+    y = F.hardtanh(t, 0.0, clip) if act else t
+    y.backward(dy)
+    mean, invstd, scale, shift = R.bn_eval_coeffs(rm, rv, w, b, eps)
+    yr = R.bn_apply(x, scale, shift, None, act is not None, clip)
+    torch.testing.assert_close(yr, y.detach(), atol=1e-12, rtol=1e-12)
+    mask = R.bn_mask_from_x(x, scale, shift, clip) if act else None
+    bs = R.bn_bwd_moments(dy, x, mean, mask)
+    a, bb, cc, dw, db = R.bn_bwd_coeffs(bs, m, w, mean, invstd, False)
+    assert not bb.any() and not cc.any()
+    dx, _ = R.bn_bwd_apply(dy, x, a, bb, cc, mask)
+    torch.testing.assert_close(dx, xl.grad, atol=1e-12, rtol=1e-12)
+    torch.testing.assert_close(dw, wl.grad, atol=1e-11, rtol=1e-11)
+    torch.testing.assert_close(db, bl.grad, atol=1e-11, rtol=1e-11)
+
+
+def test_bn_refs_on_the_thresholds_and_on_a_dead_channel():
+    # masks are strict at both ends
+    y = torch.tensor([[-1.0, 0.0, 0.5, 6.0, 7.0]])
+    assert R.bn_mask_from_y(y, 6.0).tolist() == [[False, False, True, False, False]]
+    assert R.bn_mask_from_y(y).tolist() == [[False, False, True, True, True]]
+    # a constant channel: the variance is clamped at 0 and invstd = 1/sqrt(eps as fp32 holds it)
+    x = torch.full((5, 2), 0.3, dtype=torch.float64)
+    x[:, 1] = 0.0
+    mean, var, invstd, scale, shift = R.bn_fwd_coeffs(R.bn_moments(x), None, None, 1e-5)
+    assert not var.any()
+    assert invstd[0].item() == 1.0 / float(torch.tensor(1e-5, dtype=torch.float32)) ** 0.5
+    # one row: the running variance takes the biased value
+    _, nrv = R.bn_running_update(torch.zeros(2), torch.ones(2), mean, var, 1, 0.5)
+    assert nrv.tolist() == [0.5, 0.5]
+
+
 def test_bn_relu_pool_refs_match_autograd():
     torch.manual_seed(0)
     n, c, h, w = 2, 8, 7, 6
