@@ -1,4 +1,4 @@
-"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B."""
+"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B, ConvNeXt V2."""
 from __future__ import annotations
 
 from typing import Callable, Dict
@@ -8,7 +8,9 @@ import torch.nn as nn
 from .mobilenetv2 import (HeadPool, InvertedResidual, MobileNetV2, mobilenet_v2, mobilenet_v2_224,
                           mobilenet_v2_nobn)
 from .resnet import BasicBlock, Bottleneck, ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
-from .convnext import ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, convnext_test, convnext_tiny
+from .convnext import (ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, convnext_test, convnext_tiny,
+                       convnextv2_base, convnextv2_large, convnextv2_nano, convnextv2_pico, convnextv2_test,
+                       convnextv2_tiny)
 from .vit import VisionTransformer, vit_b_16, vit_tiny
 from .layer_decay import layer_decay_scales, layer_ids
 
@@ -27,6 +29,12 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
     "convnext_small": convnext_small,
     "convnext_base": convnext_base,
     "convnext_test": convnext_test,
+    "convnextv2_pico": convnextv2_pico,
+    "convnextv2_nano": convnextv2_nano,
+    "convnextv2_tiny": convnextv2_tiny,
+    "convnextv2_base": convnextv2_base,
+    "convnextv2_large": convnextv2_large,
+    "convnextv2_test": convnextv2_test,
 }
 
 # Default input geometry per model (C, H, W) and class count.
@@ -45,6 +53,12 @@ INPUT_SHAPES = {
     "convnext_small": ((3, 224, 224), 1000),
     "convnext_base": ((3, 224, 224), 1000),
     "convnext_test": ((3, 32, 32), 10),
+    "convnextv2_pico": ((3, 224, 224), 1000),
+    "convnextv2_nano": ((3, 224, 224), 1000),
+    "convnextv2_tiny": ((3, 224, 224), 1000),
+    "convnextv2_base": ((3, 224, 224), 1000),
+    "convnextv2_large": ((3, 224, 224), 1000),
+    "convnextv2_test": ((3, 32, 32), 10),
 }
 
 
@@ -69,4 +83,5 @@ __all__ = ["MODELS", "INPUT_SHAPES", "build_model", "classifier_name", "layer_id
            "mobilenet_v2", "mobilenet_v2_nobn", "mobilenet_v2_224", "ResNet", "BasicBlock", "Bottleneck", "resnet18",
            "resnet34", "resnet50", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
            "vit_tiny", "ConvNeXt", "ConvNeXtBlock", "convnext_tiny", "convnext_small", "convnext_base",
-           "convnext_test"]
+           "convnext_test", "convnextv2_pico", "convnextv2_nano", "convnextv2_tiny", "convnextv2_base",
+           "convnextv2_large", "convnextv2_test"]

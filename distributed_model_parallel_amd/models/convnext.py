@@ -38,6 +38,7 @@ import torch.nn as nn
 from ..ops.depthwise7 import DepthwiseConv7x7
 from ..ops.drop_path import sample_scales
 from ..ops.fused import GradSlot, grad_tap
+from ..ops.grn import GRN, mlp_grn_residual_w
 from ..ops.layernorm import LayerNorm
 from ..ops.linear import Linear, mlp_residual_w
 from ..ops.patch_embed import PatchEmbed
@@ -57,9 +58,10 @@ def _as_tokens(y: torch.Tensor) -> torch.Tensor:
 
 
 class ConvNeXtBlock(nn.Module):
-    """y = x + s[b] * gamma * fc2(gelu(fc1(LN(dwconv7(x)))))"""
+    """y = x + s[b] * gamma * fc2(gelu(fc1(LN(dwconv7(x))))); with ``grn`` (V2):
+    y = x + s[b] * fc2(GRN(gelu(fc1(LN(dwconv7(x)))))), no layer scale."""
 
-    def __init__(self, dim: int, drop_path: float = 0.0, layer_scale: float = 1e-6):
+    def __init__(self, dim: int, drop_path: float = 0.0, layer_scale: float = 1e-6, grn: bool = False):
         super().__init__()
         if not 0.0 <= drop_path < 1.0:
             raise ValueError(f"drop_path must be in [0, 1), got {drop_path}")
@@ -68,7 +70,10 @@ class ConvNeXtBlock(nn.Module):
         self.norm = LayerNorm(dim, eps=1e-6)
         self.fc1 = Linear(dim, 4 * dim)
         self.fc2 = Linear(4 * dim, dim)
-        self.gamma = nn.Parameter(torch.full((dim,), float(layer_scale)))
+        if grn:
+            self.grn = GRN(4 * dim)
+        else:
+            self.gamma = nn.Parameter(torch.full((dim,), float(layer_scale)))
 
     def folded_fc2(self):
         """(W2', b2', W2'^T or None): fc2's operands with gamma folded in.
@@ -95,13 +100,16 @@ class ConvNeXtBlock(nn.Module):
         slot = GradSlot() if train else None
         h = _as_tokens(self.dwconv(_as_image(x, hw), slot))
         h = self.norm(h)
+        if hasattr(self, "grn"):
+            return mlp_grn_residual_w(h, grad_tap(x, slot), self.fc1.weight, self.fc1.bias, self.grn.gamma,
+                                      self.grn.beta, self.fc2.weight, self.fc2.bias, s)
         w2, b2, w2_t = self.folded_fc2()
         return mlp_residual_w(h, grad_tap(x, slot), self.fc1.weight, self.fc1.bias, w2, b2, s, w2_t)
 
 
 class ConvNeXt(nn.Module):
     def __init__(self, depths: Sequence[int], dims: Sequence[int], num_classes: int = 1000,
-                 drop_path_rate: float = 0.0, layer_scale: float = 1e-6, in_chans: int = 3):
+                 drop_path_rate: float = 0.0, layer_scale: float = 1e-6, in_chans: int = 3, grn: bool = False):
         super().__init__()
         if len(depths) != len(dims) or not depths:
             raise ValueError("ConvNeXt: depths and dims must have the same, non-zero length")
@@ -118,7 +126,7 @@ class ConvNeXt(nn.Module):
         rates = [drop_path_rate * i / max(1, total - 1) for i in range(total)]
         it = iter(rates)
         self.stages = nn.ModuleList(
-            nn.ModuleList(ConvNeXtBlock(dim, next(it), layer_scale) for _ in range(depth))
+            nn.ModuleList(ConvNeXtBlock(dim, next(it), layer_scale, grn) for _ in range(depth))
             for depth, dim in zip(depths, dims))
         self.norm = LayerNorm(dims[-1], eps=1e-6)
         self.head = nn.Linear(dims[-1], num_classes)
@@ -163,3 +171,33 @@ def convnext_base(num_classes: int = 1000, **kw) -> ConvNeXt:
 def convnext_test(num_classes: int = 10, **kw) -> ConvNeXt:
     """Small config for CPU tests (32-pixel input)."""
     return ConvNeXt((1, 1, 2, 1), (8, 16, 32, 64), num_classes, **kw)
+
+
+# ConvNeXt V2 (Woo et al. 2023): the same trunk with GRN in the MLP and no
+# layer scale; pico 9,066,280 / tiny 28,635,496 / base 88,717,800 parameters at
+# 1000 classes.  GRN itself is a torch composition (ops/grn.py: no native
+# kernel), and with it between GELU and fc2 the block's MLP runs on
+# ops/linear.py's linear_gelu / linear, not on the gemm_xl epilogues.
+def convnextv2_pico(num_classes: int = 1000, **kw) -> ConvNeXt:
+    return ConvNeXt((2, 2, 6, 2), (64, 128, 256, 512), num_classes, grn=True, **kw)
+
+
+def convnextv2_nano(num_classes: int = 1000, **kw) -> ConvNeXt:
+    return ConvNeXt((2, 2, 8, 2), (80, 160, 320, 640), num_classes, grn=True, **kw)
+
+
+def convnextv2_tiny(num_classes: int = 1000, **kw) -> ConvNeXt:
+    return ConvNeXt((3, 3, 9, 3), (96, 192, 384, 768), num_classes, grn=True, **kw)
+
+
+def convnextv2_base(num_classes: int = 1000, **kw) -> ConvNeXt:
+    return ConvNeXt((3, 3, 27, 3), (128, 256, 512, 1024), num_classes, grn=True, **kw)
+
+
+def convnextv2_large(num_classes: int = 1000, **kw) -> ConvNeXt:
+    return ConvNeXt((3, 3, 27, 3), (192, 384, 768, 1536), num_classes, grn=True, **kw)
+
+
+def convnextv2_test(num_classes: int = 10, **kw) -> ConvNeXt:
+    """convnext_test with GRN."""
+    return ConvNeXt((1, 1, 2, 1), (8, 16, 32, 64), num_classes, grn=True, **kw)
