@@ -1,4 +1,5 @@
-"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B, ConvNeXt V2."""
+"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B, ConvNeXt V2,
+Swin-T/S/B."""
 from __future__ import annotations
 
 from typing import Callable, Dict
@@ -12,6 +13,7 @@ from .convnext import (ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, c
                        convnextv2_base, convnextv2_large, convnextv2_nano, convnextv2_pico, convnextv2_test,
                        convnextv2_tiny)
 from .vit import VisionTransformer, vit_b_16, vit_tiny
+from .swin import SwinTransformer, swin_base, swin_small, swin_test, swin_tiny
 from .layer_decay import layer_decay_scales, layer_ids
 
 MODELS: Dict[str, Callable[..., nn.Module]] = {
@@ -35,6 +37,10 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
     "convnextv2_base": convnextv2_base,
     "convnextv2_large": convnextv2_large,
     "convnextv2_test": convnextv2_test,
+    "swin_tiny": swin_tiny,
+    "swin_small": swin_small,
+    "swin_base": swin_base,
+    "swin_test": swin_test,
 }
 
 # Default input geometry per model (C, H, W) and class count.
@@ -59,6 +65,10 @@ INPUT_SHAPES = {
     "convnextv2_base": ((3, 224, 224), 1000),
     "convnextv2_large": ((3, 224, 224), 1000),
     "convnextv2_test": ((3, 32, 32), 10),
+    "swin_tiny": ((3, 224, 224), 1000),
+    "swin_small": ((3, 224, 224), 1000),
+    "swin_base": ((3, 224, 224), 1000),
+    "swin_test": ((3, 32, 32), 10),
 }
 
 
@@ -72,7 +82,7 @@ def build_model(name: str, **kw) -> nn.Module:
 def classifier_name(model: nn.Module) -> str:
     """Name of the model's classifier (its last, class-count-shaped layer): the
     prefix of the checkpoint entries ``load_weights(reset_head=True)`` may drop."""
-    for cls, name in ((VisionTransformer, "head"), (ConvNeXt, "head"), (ResNet, "fc"), (MobileNetV2, "linear")):
+    for cls, name in ((VisionTransformer, "head"), (ConvNeXt, "head"), (SwinTransformer, "head"), (ResNet, "fc"), (MobileNetV2, "linear")):
         if isinstance(model, cls):
             return name
     raise ValueError(f"classifier_name: unknown model class {type(model).__name__}")
@@ -84,4 +94,5 @@ __all__ = ["MODELS", "INPUT_SHAPES", "build_model", "classifier_name", "layer_id
            "resnet34", "resnet50", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
            "vit_tiny", "ConvNeXt", "ConvNeXtBlock", "convnext_tiny", "convnext_small", "convnext_base",
            "convnext_test", "convnextv2_pico", "convnextv2_nano", "convnextv2_tiny", "convnextv2_base",
-           "convnextv2_large", "convnextv2_test"]
+           "convnextv2_large", "convnextv2_test", "SwinTransformer", "swin_tiny", "swin_small", "swin_base",
+           "swin_test"]

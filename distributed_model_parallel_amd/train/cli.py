@@ -72,8 +72,8 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
     if not 0.0 <= args.drop_path < 1.0:
         parser.error("--drop-path must be in [0, 1)")
     if args.drop_path > 0:
-        if not args.arch.startswith(("vit", "convnext")):
-            parser.error(f"--drop-path is for ViT archs only (vit_b_16, vit_tiny) and ConvNeXt (convnext_*), "
+        if not args.arch.startswith(("vit", "convnext", "swin")):
+            parser.error(f"--drop-path is for ViT archs only (vit_b_16, vit_tiny), ConvNeXt (convnext_*) and Swin (swin_*), "
                          f"not --arch {args.arch}")
     if args.image_size is not None:
         if not args.arch.startswith("vit"):
@@ -332,8 +332,8 @@ def _datasets(args):
 def _synthetic_kind(args) -> str:
     """Synthetic data of the dataset type's shape -- except for a ViT, whose position
     embedding fixes the input size: it gets data of the model's own shape and class count
-    (and so does a ConvNeXt: convnext_test is a 32-pixel model)."""
-    if args.arch.startswith(("vit", "convnext")):
+    (and so do a ConvNeXt and a Swin: convnext_test and swin_test are 32-pixel models)."""
+    if args.arch.startswith(("vit", "convnext", "swin")):
         from ..models import INPUT_SHAPES
         return "SyntheticCIFAR" if INPUT_SHAPES[args.arch][0][1] == 32 else "Synthetic"
     cifar = args.dataset_type in ("CIFAR10", "SyntheticCIFAR")
@@ -345,7 +345,7 @@ def _lr_steps(args):
 
 
 def _num_classes(args) -> int:
-    if (args.synthetic or not args.data) and args.arch.startswith(("vit", "convnext")):
+    if (args.synthetic or not args.data) and args.arch.startswith(("vit", "convnext", "swin")):
         return 10 if _synthetic_kind(args) == "SyntheticCIFAR" else 1000
     return {"CIFAR10": 10, "SyntheticCIFAR": 10, "CUB200": 200, "Place365": 365}.get(
         args.dataset_type, 10 if (args.synthetic or not args.data) and args.arch.startswith("mobilenet") else 1000)
