@@ -319,6 +319,17 @@ void lars_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, co
 int64_t lars_chunk_elems();   // most elements of one work item (one block of the norm / update kernels)
 int64_t lars_fold_threads();  // lanes that fold one tensor's partials in lars_trust
 
+// ---- optim/fused_lamb.hip ----
+void lamb_moments(const c10::optional<at::Tensor>& master, at::Tensor& exp_avg, at::Tensor& exp_avg_sq,
+                  const at::Tensor& grad, const at::Tensor& param, const at::Tensor& items,
+                  const at::Tensor& tensors, const at::Tensor& hyper, at::Tensor& partials, double beta1,
+                  double beta2, double eps, double weight_decay);
+void lamb_trust(const at::Tensor& partials, const at::Tensor& tensors, at::Tensor& coef, double weight_decay);
+void lamb_flat_step(const c10::optional<at::Tensor>& master, const at::Tensor& exp_avg,
+                    const at::Tensor& exp_avg_sq, at::Tensor& param, const at::Tensor& items,
+                    const at::Tensor& coef, const at::Tensor& hyper, double lr, double eps,
+                    const c10::optional<at::Tensor>& ema, double ema_decay);
+
 // ---- optim/fused_sgd.hip ----
 void sgd_flat_step(const c10::optional<at::Tensor>& master, at::Tensor& mom, const at::Tensor& grad,
                    at::Tensor& param, double lr, double wd, double momentum, double dampening, bool nesterov,

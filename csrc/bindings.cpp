@@ -376,6 +376,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("lars_chunk_elems", &dmp::lars_chunk_elems);
   m.def("lars_fold_threads", &dmp::lars_fold_threads);
+  m.def("lamb_moments", &dmp::lamb_moments, py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
+        py::arg("grad"), py::arg("param"), py::arg("items"), py::arg("tensors"), py::arg("hyper"),
+        py::arg("partials"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        "Adam's moments updated in place; partials[i] = {sum w^2, sum u^2} of the direction u over work item i",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("lamb_trust", &dmp::lamb_trust, py::arg("partials"), py::arg("tensors"), py::arg("coef"),
+        py::arg("weight_decay"),
+        "coef[t] = {|w| / |u|, weight decay, |w|, |u|} of tensor t; {1, 0, ..} for an excluded tensor",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("lamb_flat_step", &dmp::lamb_flat_step, py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
+        py::arg("param"), py::arg("items"), py::arg("coef"), py::arg("hyper"), py::arg("lr"), py::arg("eps"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0,
+        py::call_guard<py::gil_scoped_release>());
 
   // ---- coalesced movement ----
   m.def("multi_copy", &dmp::multi_copy,

@@ -1,5 +1,5 @@
-// What the flat step kernels (fused_sgd.hip, fused_adamw.hip, fused_lars.hip)
-// share.  Host side: the argument checks of one step over the flats of a dtype
+// What the flat step kernels (fused_sgd.hip, fused_adamw.hip, fused_lars.hip,
+// fused_lamb.hip) share.  Host side: the argument checks of one step over the flats of a dtype
 // group, the choice of the kernel's <G, P, MASTER, EMA> instantiation and the
 // grid-stride grid.  Device side: the weights in and out, and the optional
 // weight EMA every step kernel updates in its own pass,
@@ -79,7 +79,7 @@ inline FlatStep flat_step_args(const c10::optional<at::Tensor>& master, const at
 }
 
 // An fp32 state flat (momentum, exp_avg, exp_avg_sq) of the step's size on its device.
-inline float* check_flat_state(at::Tensor& t, const char* name, const FlatStep& fs) {
+inline float* check_flat_state(const at::Tensor& t, const char* name, const FlatStep& fs) {
   check_flat(t, name);
   TORCH_CHECK(t.scalar_type() == at::kFloat && t.numel() == fs.n && t.get_device() == fs.dev, name,
               " must be an fp32 flat of the parameters' size on the parameters' device");

@@ -18,7 +18,7 @@
 // (ddp/reducer.cpp kAlignElems, the list layout of ops/optim.py), so an
 // 8-element vector belongs to one tensor and a slot's sum of squares is its
 // tensor's.  The host cuts every slot into work items of at most kChunkVec
-// vectors, once per layout (the "plan"):
+// vectors, once per layout (the "plan", flat_plan.h, shared with fused_lamb.hip):
 //   items   int32 [I, 3]  first vector, vector count (<= kChunkVec), tensor
 //   tensors int32 [T, 3]  first item, item count, adapted (1) / excluded (0)
 // The kernels check each plan entry against the buffers' sizes and skip what
@@ -30,28 +30,11 @@
 #include <ATen/hip/HIPContext.h>
 #include "../api.h"
 #include "../common.h"
+#include "flat_plan.h"
 #include "flat_step.h"
 
 namespace dmp {
 namespace {
-
-constexpr int kVecPerLane = 4;                      // norm kernel: vectors in flight per lane
-constexpr int kChunkVec = kThreads * kVecPerLane;   // 1024 vectors = 8192 elements per work item
-constexpr int kItemCols = 3, kTensorCols = 3, kCoefCols = 4;
-constexpr int kTrust = 0, kDecay = 1, kWNorm = 2, kGNorm = 3;  // coef[] columns
-
-// The block's work item, or a count of 0 when the entry does not fit the flat.
-struct Item {
-  int first, count, tensor;
-};
-__device__ __forceinline__ Item load_item(const int32_t* __restrict__ items, int64_t nvec, int ntensors) {
-  const int32_t* it = items + (int64_t)blockIdx.x * kItemCols;
-  Item r{it[0], it[1], it[2]};
-  const bool ok = r.first >= 0 && r.count >= 0 && r.count <= kChunkVec && (int64_t)r.first + r.count <= nvec &&
-                  r.tensor >= 0 && r.tensor < ntensors;
-  if (!ok) r.count = 0;
-  return r;
-}
 
 // Block b reduces its item: partials[b] = {sum g^2, sum w^2}.  Every lane adds
 // its (up to) 4 x 8 squares in element order, the wave and the block fold in a
@@ -170,13 +153,6 @@ __global__ __launch_bounds__(kThreads) void lars_flat_kernel(float* __restrict__
     store_weights<MASTER>(master, param, o, w);
     ema_update<EMA>(ema, o, w, omd);
   }
-}
-
-void check_plan(const at::Tensor& t, const char* name, at::ScalarType dtype, int64_t cols, int dev) {
-  check_flat(t, name);
-  TORCH_CHECK(t.scalar_type() == dtype && t.dim() == 2 && t.size(1) == cols && t.size(0) <= INT32_MAX &&
-                  t.get_device() == dev,
-              name, " must be a ", dtype, " [n, ", cols, "] tensor on the parameters' device");
 }
 
 // The common checks, and that a plan's int32 vector indices reach every vector of the flats.

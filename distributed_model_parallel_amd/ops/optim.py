@@ -1,28 +1,31 @@
-"""Flat optimizers: torch.optim.SGD / torch.optim.AdamW semantics and LARS, a
-constant number of HIP launches per dtype group.
+"""Flat optimizers: torch.optim.SGD / torch.optim.AdamW semantics, LARS and
+LAMB, a constant number of HIP launches per dtype group.
 
-``FlatSGD`` / ``FlatAdamW`` / ``FlatLARS`` work on the flat parameter /
+``FlatSGD`` / ``FlatAdamW`` / ``FlatLARS`` / ``FlatLAMB`` work on the flat parameter /
 gradient buffers of ``DistributedDataParallel(..., flat_parameters=True)``:
 gradients there are already RCCL-averaged bucket views, parameters are views
 of a flat buffer with the same layout, so the update of all 161 ResNet-50
 tensors is a single vectorised pass (``csrc/optim/fused_sgd.hip``,
-``csrc/optim/fused_adamw.hip``, ``csrc/optim/fused_lars.hip``, on the shared
-host path and device helpers of ``csrc/optim/flat_step.h``).
-``MasterSGD`` / ``MasterAdamW`` / ``MasterLARS`` build the same kind of flat
+``csrc/optim/fused_adamw.hip``, ``csrc/optim/fused_lars.hip``,
+``csrc/optim/fused_lamb.hip``, on the shared host path and device helpers of
+``csrc/optim/flat_step.h`` and the per-tensor plan of ``csrc/optim/flat_plan.h``).
+``MasterSGD`` / ``MasterAdamW`` / ``MasterLARS`` / ``MasterLAMB`` build the same kind of flat
 buffers for any parameter list.  bf16 parameter groups keep an fp32 master copy
 and fp32 optimizer state inside the optimizer; the kernel writes the bf16
 working weights back in the same pass.
 
-The six classes are a layout (``_DDPLayout`` / ``_ListLayout``: where the
+The eight classes are a layout (``_DDPLayout`` / ``_ListLayout``: where the
 flats come from, how state follows a bucket rebuild, checkpoint format) times
-an update rule (``_SGDRule`` / ``_AdamWRule`` / ``_LARSRule``), on the shared
+an update rule (``_SGDRule`` / ``_AdamWRule`` / ``_LARSRule`` / ``_LAMBRule``), on the shared
 ``_FlatOptimizer`` step.
 
 Reference parity: SGD(lr, momentum 0.9, weight_decay 1e-4) at
 ``model_parallel.py:105`` / ``data_parallel.py:90``.  AdamW
 with decoupled decay off for biases / norm weights and global-norm clipping is
 what every ViT recipe trains with; LARS (per-tensor trust ratios from a
-segmented norm over the flats) is what large-batch ResNet recipes train with.
+segmented norm over the flats) is what large-batch ResNet recipes train with,
+LAMB (AdamW's direction with such a trust ratio) what large-batch transformer
+and ConvNeXt recipes train with.
 
 Every class can keep an exponential moving average of the weights
 (``ema_decay``): an fp32 flat per group, averaged over the fp32 MASTERS (a bf16
@@ -662,17 +665,13 @@ class _AdamWRule:
             self._masks, self._mask_key = masks, key
         return self._masks
 
-    def _update(self, groups: List[dict]) -> None:
+    def _prepare(self, groups: List[dict], devs: List[torch.device]) -> None:
+        """The launches before the update: the gradient's sum of squares per
+        group when clipping is on, then ``adamw_prepare`` per device (step count,
+        bias corrections, gradient norm and clip coefficient into ``hyper``)."""
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         clip = float(g["max_grad_norm"] or 0.0)
-        devs = self._clip_devices(groups)
-        if not groups:
-            return
-        masks = self._decay_masks(groups)
-        # a step that has ever run scaled keeps reading the device tables (a captured one does anyway)
-        scaled = self.lr_scaled or self._lr_key == (self._layout_id(), len(groups))
-        scales = self._lr_tensors(groups) if scaled else [None] * len(groups)
         part = None
         if clip > 0:
             part = self._partials
@@ -691,6 +690,18 @@ class _AdamWRule:
                                                             float(b1), float(b2))
             else:
                 _adamw_prepare_reference(part, ds["hyper"], ds["step"], clip, b1, b2)
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        devs = self._clip_devices(groups)
+        if not groups:
+            return
+        masks = self._decay_masks(groups)
+        # a step that has ever run scaled keeps reading the device tables (a captured one does anyway)
+        scaled = self.lr_scaled or self._lr_key == (self._layout_id(), len(groups))
+        scales = self._lr_tensors(groups) if scaled else [None] * len(groups)
+        self._prepare(groups, devs)
         for st, mask, sc in zip(groups, masks, scales):
             pflat = st["param"]
             hyper = self._dev_state[pflat.device]["hyper"]
@@ -728,56 +739,30 @@ class _AdamWRule:
             ds["step"].fill_(int(n))
 
 
-# coef[] columns written by lars_trust (csrc/optim/fused_lars.hip): trust ratio, weight decay, |w|, |g|
+# coef[] columns written by lars_trust / lamb_trust (csrc/optim/flat_plan.h): trust ratio, weight decay, |w|,
+# |g| (LARS) or |u| (LAMB)
 _TRUST, _COEF_COLS = 0, 4
 
 
-class _LARSRule:
-    """LARS (You et al. 2017) with momentum: per tensor
-    ``trust = eta |w| / (|g| + wd |w| + eps)`` (1 where ``|w|`` or ``|g|`` is
-    exactly 0), ``d = trust (g + wd w)``, ``m <- mu m + d``, ``w <- w - lr m``.
-    With ``exclude_1d`` parameters with ``ndim <= 1`` (biases, BatchNorm /
-    LayerNorm weights) get ``trust = 1`` and no weight decay: ``d = g``.
+class _TensorPlan:
+    """The segmented per-tensor plan of the rules with a trust ratio
+    (``_LARSRule``, ``_LAMBRule``) and the read-outs of its ``coef``."""
 
-    The norms are taken over the fp32 masters (the fp32 parameters where there
-    is no master) and the averaged gradient, per tensor, by a segmented
-    reduction over the flats: three launches per dtype group whatever the number
-    of tensors.  Norms and trust ratios stay on the device, so ``step()`` never
-    syncs the host and a step captured into a hipGraph stays correct on replay;
-    ``lr`` is a host scalar outside the momentum, as in the SGD classes (the
-    schedules write ``param_groups[0]['lr']``).  Gradients are equal on every
-    rank after the all-reduce and the norms are per tensor, so LARS needs no
-    communication of its own and works per stage in a pipeline.
-    """
-
-    KIND = "lars"
-    STATE_KEYS = ("momentum",)
-
-    def _lars_defaults(self, lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d) -> dict:
-        if lr < 0 or momentum < 0 or weight_decay < 0 or trust_coefficient <= 0 or eps < 0:
-            raise ValueError("%s: lr, momentum, weight_decay and eps must not be negative, "
-                             "trust_coefficient must be positive" % self._name())
+    def _init_plan(self, exclude_1d: bool) -> None:
         self.exclude_1d = bool(exclude_1d)
         self._plans: List[dict] = []
         self._plan_key = None
         self._stepped = False
-        return dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
-                    trust_coefficient=trust_coefficient, eps=eps)
 
-    def add_param_group(self, param_group):
-        if self.param_groups:
-            raise ValueError("%s supports one param group (adaptation is switched per parameter by "
-                             "exclude_1d)" % self._name())
-        super().add_param_group(param_group)
-
-    def _lars_plans(self, groups: List[dict]) -> List[dict]:
+    def _tensor_plans(self, groups: List[dict]) -> List[dict]:
         """Per group, the work items of the segmented reduction and the update,
         built on the host once per layout and kept on the group's device:
 
         ``items``    int32 [I, 3]: first vector, vector count, tensor -- every
                      parameter's slot cut into pieces of at most
                      ``lars_chunk_elems()`` elements, none across a boundary
-        ``tensors``  int32 [T, 3]: first item, item count, adapted?  (``_slots`` order)
+        ``tensors``  int32 [T, 3]: first item, item count, adapted?  (``_slots`` order;
+                     with ``exclude_1d`` a parameter with ``ndim <= 1`` is not adapted)
         ``partials`` fp32 [I, 2], ``coef`` fp32 [T, 4]: the kernels' outputs
         """
         key = (self._layout_id(), len(groups))
@@ -808,23 +793,6 @@ class _LARSRule:
         self._plans, self._plan_key = plans, key
         return plans
 
-    def _update(self, groups: List[dict]) -> None:
-        g = self.param_groups[0]
-        if not groups:
-            return
-        for st, plan in zip(groups, self._lars_plans(groups)):
-            pflat, master = st["param"], st.get("master")
-            if pflat.is_cuda:
-                C = _native.require(self._name())
-                C.lars_norm_partials(master, st["grad"], pflat, plan["items"], plan["partials"])
-                C.lars_trust(plan["partials"], plan["tensors"], plan["coef"], float(g["trust_coefficient"]),
-                             float(g["weight_decay"]), float(g["eps"]))
-                C.lars_flat_step(master, st["momentum"], st["grad"], pflat, plan["items"], plan["coef"],
-                                 float(g["lr"]), float(g["momentum"]), *self._ema_args(st))
-            else:
-                _lars_reference(master, st["momentum"], st["grad"], pflat, plan["spans"], plan["coef"], g)
-        self._stepped = True
-
     @property
     def last_trust_ratios(self) -> Optional[List[torch.Tensor]]:
         """The last step's trust ratios: one fp32 device tensor per dtype group,
@@ -847,8 +815,124 @@ class _LARSRule:
         return float(vals.min()), float(vals.max())
 
 
+class _LARSRule(_TensorPlan):
+    """LARS (You et al. 2017) with momentum: per tensor
+    ``trust = eta |w| / (|g| + wd |w| + eps)`` (1 where ``|w|`` or ``|g|`` is
+    exactly 0), ``d = trust (g + wd w)``, ``m <- mu m + d``, ``w <- w - lr m``.
+    With ``exclude_1d`` parameters with ``ndim <= 1`` (biases, BatchNorm /
+    LayerNorm weights) get ``trust = 1`` and no weight decay: ``d = g``.
+
+    The norms are taken over the fp32 masters (the fp32 parameters where there
+    is no master) and the averaged gradient, per tensor, by a segmented
+    reduction over the flats: three launches per dtype group whatever the number
+    of tensors.  Norms and trust ratios stay on the device, so ``step()`` never
+    syncs the host and a step captured into a hipGraph stays correct on replay;
+    ``lr`` is a host scalar outside the momentum, as in the SGD classes (the
+    schedules write ``param_groups[0]['lr']``).  Gradients are equal on every
+    rank after the all-reduce and the norms are per tensor, so LARS needs no
+    communication of its own and works per stage in a pipeline.
+    """
+
+    KIND = "lars"
+    STATE_KEYS = ("momentum",)
+
+    def _lars_defaults(self, lr, momentum, weight_decay, trust_coefficient, eps, exclude_1d) -> dict:
+        if lr < 0 or momentum < 0 or weight_decay < 0 or trust_coefficient <= 0 or eps < 0:
+            raise ValueError("%s: lr, momentum, weight_decay and eps must not be negative, "
+                             "trust_coefficient must be positive" % self._name())
+        self._init_plan(exclude_1d)
+        return dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                    trust_coefficient=trust_coefficient, eps=eps)
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("%s supports one param group (adaptation is switched per parameter by "
+                             "exclude_1d)" % self._name())
+        super().add_param_group(param_group)
+
+    def _lars_plans(self, groups: List[dict]) -> List[dict]:
+        return self._tensor_plans(groups)
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        if not groups:
+            return
+        for st, plan in zip(groups, self._lars_plans(groups)):
+            pflat, master = st["param"], st.get("master")
+            if pflat.is_cuda:
+                C = _native.require(self._name())
+                C.lars_norm_partials(master, st["grad"], pflat, plan["items"], plan["partials"])
+                C.lars_trust(plan["partials"], plan["tensors"], plan["coef"], float(g["trust_coefficient"]),
+                             float(g["weight_decay"]), float(g["eps"]))
+                C.lars_flat_step(master, st["momentum"], st["grad"], pflat, plan["items"], plan["coef"],
+                                 float(g["lr"]), float(g["momentum"]), *self._ema_args(st))
+            else:
+                _lars_reference(master, st["momentum"], st["grad"], pflat, plan["spans"], plan["coef"], g)
+        self._stepped = True
+
+
+class _LAMBRule(_TensorPlan, _AdamWRule):
+    """LAMB (You et al. 2020; timm's ``Lamb`` with ``always_adapt=False`` and
+    ``trust_clip=False``): AdamW's direction rescaled per tensor.  After
+    ``clip_grad_norm_(max_grad_norm)`` over all groups, per element
+    ``u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd w`` from Adam's moments,
+    per tensor ``trust = |w| / |u|`` (1 where ``|w|`` or ``|u|`` is exactly 0)
+    and ``w <- w - lr trust u``.  With ``exclude_1d`` parameters with
+    ``ndim <= 1`` get no weight decay and ``trust = 1``: plain Adam.
+
+    The state is AdamW's (``exp_avg``, ``exp_avg_sq``; the step count, bias
+    corrections and clip coefficient in the device ``hyper`` that
+    ``adamw_prepare`` writes), the per-tensor plan is LARS's, and the three
+    kernels of ``csrc/optim/fused_lamb.hip`` run between them: three launches
+    per dtype group after the two of the clip and the step count, no host sync,
+    correct on the replay of a captured step.  ``lr`` is a host scalar.
+    """
+
+    KIND = "lamb"
+    STATE_KEYS = ("exp_avg", "exp_avg_sq")
+
+    def _lamb_defaults(self, lr, betas, eps, weight_decay, max_grad_norm, exclude_1d) -> dict:
+        if not eps > 0:  # the zero padding of a slot must give u = 0 / eps = 0
+            raise ValueError("%s: eps must be positive, got %r" % (self._name(), eps))
+        self._init_plan(exclude_1d)
+        return self._adamw_defaults(lr, betas, eps, weight_decay, max_grad_norm, exclude_1d, False, False)
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("%s supports one param group (adaptation is switched per parameter by "
+                             "exclude_1d)" % self._name())
+        torch.optim.Optimizer.add_param_group(self, param_group)
+
+    def set_lr_scales(self, lr_scales) -> None:
+        raise ValueError("%s: per-parameter lr scales are not supported" % self._name())
+
+    def _update(self, groups: List[dict]) -> None:
+        g = self.param_groups[0]
+        b1, b2 = (float(b) for b in g["betas"])
+        lr, eps, wd = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
+        devs = self._clip_devices(groups)
+        if not groups:
+            return
+        plans = self._tensor_plans(groups)
+        self._prepare(groups, devs)
+        for st, plan in zip(groups, plans):
+            pflat, master = st["param"], st.get("master")
+            hyper = self._dev_state[pflat.device]["hyper"]
+            if pflat.is_cuda:
+                C = _native.require(self._name())
+                C.lamb_moments(master, st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, plan["items"],
+                               plan["tensors"], hyper, plan["partials"], b1, b2, eps, wd)
+                C.lamb_trust(plan["partials"], plan["tensors"], plan["coef"], wd)
+                C.lamb_flat_step(master, st["exp_avg"], st["exp_avg_sq"], pflat, plan["items"], plan["coef"],
+                                 hyper, lr, eps, *self._ema_args(st))
+            else:
+                _lamb_reference(master, st["exp_avg"], st["exp_avg_sq"], st["grad"], pflat, plan["spans"],
+                                plan["coef"], hyper, g)
+        self._stepped = True
+
+
 # --------------------------------------------------------------------------- #
-# the six optimizers
+# the eight optimizers
 # --------------------------------------------------------------------------- #
 def _trainable_of_one_group(params, name: str, switch: str) -> list:
     """The trainable parameters of a parameter list, or of a list of exactly one param-group dict."""
@@ -958,15 +1042,51 @@ class MasterLARS(_LARSRule, _ListLayout, _FlatOptimizer):
         self._init_layout(params, master_weights, ema_decay, ema_warmup)
 
 
+class FlatLAMB(_LAMBRule, _DDPLayout, _FlatOptimizer):
+    """LAMB on the DDP flat buffers (twin of :class:`FlatAdamW`), the optimizer of
+    large-batch transformer and ConvNeXt recipes.  ``exclude_1d`` keeps
+    parameters with ``ndim <= 1`` (biases, LayerNorm / BatchNorm weights) on
+    plain Adam without weight decay; ``max_grad_norm`` (``None`` / 0 = off)
+    clips the gradient of the whole model before the moments see it."""
+
+    def __init__(self, ddp, lr: float, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 1e-2,
+                 max_grad_norm: Optional[float] = 1.0, exclude_1d: bool = True, master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        defaults = self._lamb_defaults(lr, betas, eps, weight_decay, max_grad_norm, exclude_1d)
+        super().__init__(list(ddp._params), defaults)
+        self._init_layout(ddp, master_weights, ema_decay, ema_warmup)
+
+
+class MasterLAMB(_LAMBRule, _ListLayout, _FlatOptimizer):
+    """:class:`FlatLAMB` for ANY parameter list (twin of :class:`MasterAdamW`)."""
+
+    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 1e-2,
+                 max_grad_norm: Optional[float] = 1.0, exclude_1d: bool = True, master_weights: bool = True,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        defaults = self._lamb_defaults(lr, betas, eps, weight_decay, max_grad_norm, exclude_1d)
+        params = _trainable_of_one_group(params, "MasterLAMB",
+                                         "adaptation is switched per parameter by exclude_1d")
+        super().__init__(params, defaults)
+        self._init_layout(params, master_weights, ema_decay, ema_warmup)
+        self._clip_devices(self._groups)
+
+
 def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 0.9,
                     weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                     clip_grad_norm: float = 0.0, trust_coefficient: float = 1e-3,
                     ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                    lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None):
+                    lr_scales: Optional[Mapping[torch.nn.Parameter, float]] = None,
+                    trust_ratio: bool = False):
     """The trainer's optimizer: ``kind`` sgd | adamw | lars; ``flat`` picks the
     DDP-flat class (``target`` is the DDP wrapper) over the parameter-list one.
     ``ema_decay`` (``None`` / 0 = off) keeps a weight EMA in the optimizer;
-    ``lr_scales`` (adamw only) maps parameters to a factor on ``lr``."""
+    ``lr_scales`` (adamw only) maps parameters to a factor on ``lr``;
+    ``trust_ratio`` (adamw only) rescales AdamW's update per tensor by
+    ``|w| / |update|``, which is LAMB (not together with ``lr_scales``)."""
+    if trust_ratio and kind != "adamw":
+        raise ValueError("trust_ratio (LAMB) needs optimizer='adamw'")
+    if trust_ratio and lr_scales is not None:
+        raise ValueError("per-parameter lr scales (layer-wise lr decay) are not supported with trust_ratio (LAMB)")
     if kind in ("sgd", "lars") and clip_grad_norm:
         raise ValueError("gradient clipping needs optimizer='adamw'")
     if kind in ("sgd", "lars") and lr_scales is not None:
@@ -975,6 +1095,9 @@ def build_optimizer(kind: str, target, flat: bool, lr: float, momentum: float = 
     if kind == "sgd":
         return (FlatSGD if flat else MasterSGD)(target, lr=lr, momentum=momentum, weight_decay=weight_decay,
                                                 **ema)
+    if kind == "adamw" and trust_ratio:
+        return (FlatLAMB if flat else MasterLAMB)(target, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                  max_grad_norm=clip_grad_norm or None, **ema)
     if kind == "adamw":
         return (FlatAdamW if flat else MasterAdamW)(target, lr=lr, betas=betas, eps=eps,
                                                     weight_decay=weight_decay,
@@ -1034,6 +1157,38 @@ def _lars_reference(master: Optional[torch.Tensor], mom: torch.Tensor, grad: tor
             d = d * torch.tensor(trust, dtype=torch.float32)
         ms.mul_(g["momentum"]).add_(d)
         ws.sub_(ms, alpha=g["lr"])
+    if wf is not w:
+        w.copy_(wf.to(w.dtype))
+    if master is not None:
+        param.copy_(master.to(param.dtype))
+
+
+def _lamb_reference(master: Optional[torch.Tensor], exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                    grad: torch.Tensor, param: torch.Tensor, spans, coef: torch.Tensor, hyper: torch.Tensor,
+                    g: dict) -> None:
+    """PyTorch implementation of the three LAMB kernels, fp32 like them (norms
+    and trust ratio in double).  ``spans``: (offset, padded length, adapted?) per
+    tensor; ``coef`` [T, 4] receives {trust, weight decay, |w|, |u|}."""
+    w = master if master is not None else param
+    wf = w if w.dtype == torch.float32 else w.float()
+    b1, b2 = g["betas"]
+    wd = float(g["weight_decay"])
+    gr = grad.float() * hyper[_CLIP]
+    exp_avg.mul_(b1).add_(gr, alpha=1 - b1)
+    exp_avg_sq.mul_(b2).addcmul_(gr, gr, value=1 - b2)
+    denom = (exp_avg_sq.sqrt() / hyper[_BC2].sqrt()).add_(g["eps"])  # sqrt(v) + eps: 0 / eps = 0
+    adam = (exp_avg / hyper[_BC1]) / denom
+    for t, (off, n, adapted) in enumerate(spans):
+        ws, u = wf.narrow(0, off, n), adam.narrow(0, off, n)
+        trust, decay = 1.0, 0.0
+        if adapted:
+            decay = wd
+            u = u + decay * ws
+        wn, un = ws.double().norm(), u.double().norm()
+        if adapted and float(wn) != 0.0 and float(un) != 0.0:
+            trust = float(wn / un)
+        coef[t] = torch.tensor([trust, decay, float(wn), float(un)], dtype=torch.float32)
+        ws.sub_(u, alpha=float(torch.tensor(g["lr"], dtype=torch.float32) * torch.tensor(trust, dtype=torch.float32)))
     if wf is not w:
         w.copy_(wf.to(w.dtype))
     if master is not None:

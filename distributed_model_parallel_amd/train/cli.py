@@ -55,6 +55,10 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
         args.trust_coefficient = TRUST_COEFFICIENT
     if args.trust_coefficient <= 0:
         parser.error("--trust-coefficient must be positive")
+    if args.lamb and args.optimizer != "adamw":
+        parser.error("--lamb needs --optimizer adamw")
+    if args.lamb and args.layer_decay != 1.0:
+        parser.error("--lamb with --layer-decay is not supported")
     if not 0.0 <= args.label_smoothing < 1.0:
         parser.error("--label-smoothing must be in [0, 1)")
     if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
@@ -150,7 +154,8 @@ def _optimizer(args, target, flat: bool, lr_scales=None):
                            weight_decay=args.weight_decay, betas=args.betas, eps=args.eps,
                            clip_grad_norm=args.clip_grad_norm, trust_coefficient=trust,
                            ema_decay=getattr(args, "model_ema_decay", 0.0) or None,
-                           ema_warmup=getattr(args, "model_ema_warmup", False), lr_scales=lr_scales)
+                           ema_warmup=getattr(args, "model_ema_warmup", False), lr_scales=lr_scales,
+                           trust_ratio=getattr(args, "lamb", False))
 
 
 def _optimizer_log(args, opt) -> dict:
@@ -158,7 +163,7 @@ def _optimizer_log(args, opt) -> dict:
     extra = {}
     if args.clip_grad_norm and opt.last_grad_norm is not None:
         extra["grad_norm"] = float(opt.last_grad_norm)
-    if args.optimizer == "lars":
+    if args.optimizer == "lars" or getattr(args, "lamb", False):
         span = opt.last_trust_range()  # over the adapted tensors
         if span is not None:
             extra["trust_min"], extra["trust_max"] = span
@@ -188,6 +193,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eps", default=1e-8, type=float, help="--optimizer adamw / lars")
     p.add_argument("--trust-coefficient", default=None, type=float, metavar="ETA",
                    help=f"--optimizer lars: trust ratio = ETA |w| / (|g| + wd |w| + eps) (default {TRUST_COEFFICIENT})")
+    p.add_argument("--lamb", action="store_true",
+                   help="--optimizer adamw: LAMB, AdamW's update rescaled per tensor by |w| / |update| (biases / norm "
+                        "weights excluded), for large batches; takes --betas, --eps, --wd and --clip-grad-norm as "
+                        "AdamW does, e.g. --lr 3e-3 --wd 0.05 --eps 1e-6 --clip-grad-norm 1.0; not with --layer-decay")
     p.add_argument("--clip-grad-norm", default=0.0, type=float, metavar="X",
                    help="--optimizer adamw: clip the global gradient norm to X (0 = off)")
     p.add_argument("--label-smoothing", default=0.0, type=float, metavar="E",

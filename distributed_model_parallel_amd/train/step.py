@@ -45,6 +45,7 @@ class StepConfig:
     eps: float = 1e-8               # optimizer == "adamw" / "lars"
     clip_grad_norm: float = 0.0     # optimizer == "adamw": global-norm clipping (0 = off)
     trust_coefficient: float = 1e-3  # optimizer == "lars"
+    trust_ratio: bool = False       # optimizer == "adamw": per-tensor |w| / |update| on AdamW's step, i.e. LAMB
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
     drop_path_rate: float = 0.0     # ViT / ConvNeXt / Swin: stochastic depth, linear over the blocks (ops/drop_path.py)
     ema_decay: float = 0.0          # weight EMA inside the optimizer's step kernels (ops/optim.py); 0 = off
@@ -102,7 +103,7 @@ def _optimizer(cfg: StepConfig, target, flat: bool, lr_scales=None) -> torch.opt
     return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
                            weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
                            clip_grad_norm=cfg.clip_grad_norm, trust_coefficient=cfg.trust_coefficient,
-                           ema_decay=cfg.ema_decay or None, lr_scales=lr_scales)
+                           ema_decay=cfg.ema_decay or None, lr_scales=lr_scales, trust_ratio=cfg.trust_ratio)
 
 
 def build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:

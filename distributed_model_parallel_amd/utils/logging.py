@@ -20,7 +20,7 @@ from typing import Any, Dict, Optional
 def reference_line(epoch: int, rec: Dict[str, Any]) -> str:
     """``step:E  loss_train:..  acc1_train:..  loss_val:..  acc1_val:..[  time_per_batch:..
     time_load_perbatch:..]`` exactly in the reference's key order; ``grad_norm`` follows
-    when the run clips gradients, ``trust_min`` / ``trust_max`` under LARS, ``loss_val_ema`` /
+    when the run clips gradients, ``trust_min`` / ``trust_max`` under LARS and ``--lamb``, ``loss_val_ema`` /
     ``acc1_val_ema`` / ``ema_decay`` when it keeps a weight EMA (the reference has no such fields)."""
     parts = [f"step:{epoch}"]
     for k in ("loss_train", "acc1_train", "loss_val", "acc1_val", "time_per_batch",

@@ -14,6 +14,10 @@
 * the three LARS kernels: ``lars_norm_partials`` reads g(2) w(4) = 6 B per
   element, ``lars_trust`` reads the per-item partials (launch-bound),
   ``lars_flat_step`` moves what the SGD kernel moves, 20 B per element;
+* the three LAMB kernels: ``lamb_moments`` reads g(2) w(4) m(4) v(4) and writes
+  m(4) v(4) = 22 B per element, ``lamb_trust`` is launch-bound like
+  ``lars_trust``, ``lamb_flat_step`` reads m(4) v(4) w(4) and writes w(4) p(2)
+  = 18 B per element;
 
 on the flats of ResNet-50 (25.6 M elements) and ViT-B/16 (86.6 M), laid out
 tensor by tensor as the optimizers lay them out (every slot padded to 8
@@ -24,7 +28,8 @@ back-to-back launches each after a warm-up round; the table gives the median
 round and the min-max spread.  AdamW should reach at least 0.9x the GB/s SGD
 reaches (same access pattern; the margin is its sqrt / divide VALU work); a
 LARS step (its three kernels) should take about 1.3x the SGD kernel's time
-(26 B against 20 B per element, plus two short launches).
+(26 B against 20 B per element, plus two short launches); a LAMB step (its
+three kernels) about 1.4x the AdamW kernel's (40 B against 28 B per element).
 """
 import argparse
 import os
@@ -40,6 +45,7 @@ from distributed_model_parallel_amd.ops.optim import _SUMSQ_BLOCKS, MasterLARS  
 SIZES = {"resnet50": 25_557_032, "vit_b_16": 86_567_656}
 HBM_ACHIEVABLE_GBS = 6300.0  # streaming ceiling of an MI355X (8 TB/s peak)
 LARS = ("lars_norm_partials", "lars_trust", "lars_flat_step")
+LAMB = ("lamb_moments", "lamb_trust", "lamb_flat_step")
 
 
 def time_ms(fn, iters: int) -> float:
@@ -90,7 +96,7 @@ def main(argv=None) -> int:
         m1.zero_()
         # every rule keeps its own state: an exp_avg fed with SGD's momentum (10 g) over sqrt(exp_avg_sq)
         # makes steps that grow with the weights, and hundreds of timed launches then overflow them
-        m2, ma, ml = (torch.zeros(n, device=dev) for _ in range(3))
+        m2, ma, ml, mb, vb = (torch.zeros(n, device=dev) for _ in range(5))
         # The scaled AdamW kernel shares the unscaled one's moments (the same rule, so the state stays sane):
         # where two equal buffers lie in HBM moves this kernel by 15 %, thirty times what is compared here.
         # Layer-wise lr decay as the trainer lays it out: 14 layer ids over the tensors in order, 0.75^k
@@ -105,6 +111,7 @@ def main(argv=None) -> int:
         step = torch.zeros(1, dtype=torch.int64, device=dev)
         part = torch.zeros(1, _SUMSQ_BLOCKS, device=dev)
         items, tensors, partials, coef = plan["items"], plan["tensors"], plan["partials"], plan["coef"]
+        bpart, bcoef = torch.zeros_like(partials), torch.zeros_like(coef)  # LAMB's own: coef feeds its step
         C.adamw_prepare(None, hyper, step, 0.0, 0.9, 0.999)
         kernels = {
             "sgd_flat_step": (20.0, lambda: C.sgd_flat_step(master, m1, g, param, 1e-3, 1e-4, 0.9, 0.0, False,
@@ -118,6 +125,12 @@ def main(argv=None) -> int:
             "lars_trust": ((partials.numel() + tensors.numel() + coef.numel()) * 4 / n,
                            lambda: C.lars_trust(partials, tensors, coef, 1e-3, 1e-4, 1e-8)),
             "lars_flat_step": (20.0, lambda: C.lars_flat_step(master, ml, g, param, items, coef, 1e-3, 0.9)),
+            "lamb_moments": (22.0, lambda: C.lamb_moments(master, mb, vb, g, param, items, tensors, hyper, bpart,
+                                                          0.9, 0.999, 1e-6, 0.05)),
+            "lamb_trust": ((partials.numel() + tensors.numel() + coef.numel()) * 4 / n,
+                           lambda: C.lamb_trust(bpart, tensors, bcoef, 0.05)),
+            "lamb_flat_step": (18.0, lambda: C.lamb_flat_step(master, mb, vb, param, items, bcoef, hyper, 1e-3,
+                                                              1e-6)),
         }
         times = {k: [] for k in kernels}
         for r in range(a.rounds + 1):  # round 0 warms up every kernel at this size
@@ -143,10 +156,14 @@ def main(argv=None) -> int:
         lars = sum(med[k] for k in LARS)
         notes.append(f"{name}: {ntensors} tensors, {items.shape[0]} work items; lars (norm + trust + step) "
                      f"{lars:.4f} ms = {lars / med['sgd_flat_step']:.3f} x sgd_flat_step")
+        lamb = sum(med[k] for k in LAMB)
+        notes.append(f"{name}: lamb (moments + trust + step) {lamb:.4f} ms = "
+                     f"{lamb / med['adamw_flat_step']:.3f} x adamw_flat_step")
         assert torch.isfinite(master).all()
-        del opt, st, plan, g, master, param, m1, m2, ma, ml, mask, lr_class, lr_scales, kernels
+        del opt, st, plan, g, master, param, m1, m2, ma, ml, mb, vb, bpart, bcoef, mask, lr_class, lr_scales, kernels
     print(f"\nadamw / sgd bandwidth ratio, worst size: {worst:.3f} (target >= 0.9)")
-    print("\n".join(notes) + "\n(lars / sgd expected from the traffic: about 1.3)")
+    print("\n".join(notes) + "\n(lars / sgd expected from the traffic: about 1.3; "
+          "lamb / adamw: about 1.4)")
     return 0
 
 
