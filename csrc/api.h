@@ -272,6 +272,15 @@ std::vector<at::Tensor> gelu_bwd_bias_grad(const at::Tensor& dy, const at::Tenso
 std::vector<at::Tensor> rowscale_bias_grad(const at::Tensor& dy, const at::Tensor& row_scale, int64_t rows_per_sample,
                                            at::ScalarType out_dtype);
 
+// ---- loss/bce.hip ----
+std::vector<at::Tensor> bce_fwd(const at::Tensor& x, const at::Tensor& target, int64_t ignore_index, double scale,
+                                const c10::optional<at::Tensor>& acc, double label_smoothing,
+                                const c10::optional<at::Tensor>& target_b, double lam,
+                                const c10::optional<double>& target_thresh, bool sum_classes);
+at::Tensor bce_bwd(const at::Tensor& grad, const at::Tensor& x, const at::Tensor& target, const at::Tensor& stats,
+                   int64_t ignore_index, double label_smoothing, const c10::optional<at::Tensor>& target_b,
+                   double lam, const c10::optional<double>& target_thresh, bool sum_classes);
+
 // ---- loss/cross_entropy.hip ----
 std::vector<at::Tensor> cross_entropy_fwd(const at::Tensor& x, const at::Tensor& target,
                                           int64_t ignore_index, double scale,

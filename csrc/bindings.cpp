@@ -66,6 +66,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cross_entropy_bwd", &dmp::cross_entropy_bwd, py::arg("grad"), py::arg("x"), py::arg("target"),
         py::arg("lse"), py::arg("stats"), py::arg("ignore_index") = -100, py::arg("label_smoothing") = 0.0,
         py::arg("target_b") = py::none(), py::arg("lam") = 1.0, py::call_guard<py::gil_scoped_release>());
+  m.def("bce_fwd", &dmp::bce_fwd, py::arg("x"), py::arg("target"), py::arg("ignore_index") = -100,
+        py::arg("scale") = 1.0, py::arg("acc") = py::none(), py::arg("label_smoothing") = 0.0,
+        py::arg("target_b") = py::none(), py::arg("lam") = 1.0, py::arg("target_thresh") = py::none(),
+        py::arg("sum_classes") = false,
+        "scale * binary cross-entropy over the classes on smoothed / mixed (optionally thresholded) targets, "
+        "normalised by n_valid * C (sum_classes: n_valid); acc (fp64 [3]) += (loss, top-1 correct, top-5 correct)",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bce_bwd", &dmp::bce_bwd, py::arg("grad"), py::arg("x"), py::arg("target"), py::arg("stats"),
+        py::arg("ignore_index") = -100, py::arg("label_smoothing") = 0.0, py::arg("target_b") = py::none(),
+        py::arg("lam") = 1.0, py::arg("target_thresh") = py::none(), py::arg("sum_classes") = false,
+        py::call_guard<py::gil_scoped_release>());
   m.def("batch_mix", &dmp::batch_mix, py::arg("x"), py::arg("perm"), py::arg("lam"),
         py::arg("box") = std::vector<int64_t>{},
         "mixup (empty box): lam * x[i] + (1 - lam) * x[perm[i]]; CutMix (box = [y0, y1, x0, x1]): "

@@ -17,6 +17,15 @@ label ``target_b`` weighted ``1 - lam`` beside the first weighted ``lam``
 which is ``lam * F.cross_entropy(x, a, label_smoothing=e) + (1-lam) *
 F.cross_entropy(x, b, label_smoothing=e)``.  A row is ignored iff its first
 label is ``ignore_index``.  With the defaults the plain kernels run.
+
+``binary_cross_entropy`` (``csrc/loss/bce.hip``) is timm's ``BinaryCrossEntropy``
+on the same labels: sigmoid BCE over the classes against the dense target
+
+    d_c = e/C + (1-e) * (lam * [c == a] + (1-lam) * [c == b])
+
+thresholded to {0, 1} with ``target_thresh`` (``d_c > th``), averaged over the
+valid rows and the classes (``sum_classes``: over the rows only).  The kernels
+take the labels as indices: no dense target, no fp32 copy of the logits.
 """
 from __future__ import annotations
 
@@ -121,6 +130,12 @@ def cross_entropy_with_stats(logits: torch.Tensor, target: torch.Tensor, scale: 
     _STATS["torch"] += 1
     lf = logits.float()
     loss = _torch_ce(lf, target, -100, e, target_b, l) * scale
+    _add_stats(stats, loss, lf, target)
+    return loss
+
+
+def _add_stats(stats: torch.Tensor, loss: torch.Tensor, lf: torch.Tensor, target: torch.Tensor) -> None:
+    """stats += (loss, top-1 correct, top-min(5, C) correct) with torch's topk."""
     with torch.no_grad():
         maxk = min(5, lf.shape[1])
         pred = lf.topk(maxk, 1, True, True).indices.t()
@@ -128,4 +143,94 @@ def cross_entropy_with_stats(logits: torch.Tensor, target: torch.Tensor, scale: 
         stats[0] += loss.detach().double()
         stats[1] += correct[:1].sum().double()
         stats[2] += correct[:maxk].sum().double()
+
+
+class _BinaryCrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, scale, acc, label_smoothing, target_b, lam, thresh, sum_classes):
+        C = _native.require("binary_cross_entropy")
+        loss, stats = C.bce_fwd(logits, target, ignore_index, scale, acc, label_smoothing, target_b, lam, thresh,
+                                sum_classes)
+        if target_b is None:
+            ctx.save_for_backward(logits, target, stats)
+        else:
+            ctx.save_for_backward(logits, target, stats, target_b)
+        ctx.args = (ignore_index, label_smoothing, lam, thresh, sum_classes)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, stats, *tb = ctx.saved_tensors
+        ignore_index, e, lam, thresh, sum_classes = ctx.args
+        C = _native.require("binary_cross_entropy backward")
+        dx = C.bce_bwd(g.reshape(1), logits, target, stats, ignore_index, e, tb[0] if tb else None, lam, thresh,
+                       sum_classes)
+        return (dx,) + (None,) * 9
+
+
+def _check_thresh(target_thresh: Optional[float]) -> Optional[float]:
+    if target_thresh is None:
+        return None
+    if not 0.0 <= float(target_thresh) < 1.0:
+        raise ValueError(f"target_thresh must be in [0, 1) or None, got {target_thresh}")
+    return float(target_thresh)
+
+
+def _torch_bce(lf: torch.Tensor, target: torch.Tensor, ignore_index: int, e: float,
+               target_b: Optional[torch.Tensor], lam: float, thresh: Optional[float],
+               sum_classes: bool) -> torch.Tensor:
+    """The PyTorch composition of the same value (fp32 logits): timm's dense target, then
+    F.binary_cross_entropy_with_logits over the valid rows."""
+    C = lf.shape[1]
+    valid = target != ignore_index
+    a = torch.where(valid, target, torch.zeros_like(target))
+    b = a if target_b is None else torch.where(valid, target_b, a)
+    same = (b == a).to(lf.dtype)[:, None]
+    # both labels on one class: the label term is 1 - e whatever lam is
+    dense = lf.new_full(lf.shape, e / C)
+    dense.scatter_add_(1, a[:, None], (1.0 - e) * (same + (1.0 - same) * lam))
+    dense.scatter_add_(1, b[:, None], (1.0 - e) * (1.0 - same) * (1.0 - lam))
+    if thresh is not None:
+        dense = (dense > thresh).to(lf.dtype)
+    rows = F.binary_cross_entropy_with_logits(lf, dense, reduction="none").sum(1)
+    norm = valid.sum() * (1 if sum_classes else C)
+    return torch.where(valid, rows, torch.zeros_like(rows)).sum() / norm
+
+
+def binary_cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100,
+                         label_smoothing: float = 0.0, target_b: Optional[torch.Tensor] = None, lam: float = 1.0,
+                         target_thresh: Optional[float] = None, sum_classes: bool = False) -> torch.Tensor:
+    """Sigmoid binary cross-entropy over the classes in fp32 (timm's ``BinaryCrossEntropy``) on
+    the smoothed, mixed and optionally thresholded targets of the module docstring; the mean
+    over valid rows and classes, or with ``sum_classes`` the mean over valid rows of the class sums."""
+    e, l = _check_soft(target, label_smoothing, target_b, lam)
+    th = _check_thresh(target_thresh)
+    if _native_ce_ok(logits, target):
+        _STATS["native"] += 1
+        tb = None if target_b is None else target_b.contiguous()
+        return _BinaryCrossEntropyFn.apply(logits, target.contiguous(), int(ignore_index), 1.0, None, e, tb, l, th,
+                                           bool(sum_classes))
+    _STATS["torch"] += 1
+    return _torch_bce(logits.float(), target, ignore_index, e, target_b, l, th, bool(sum_classes))
+
+
+def binary_cross_entropy_with_stats(logits: torch.Tensor, target: torch.Tensor, scale: float, stats: torch.Tensor,
+                                    label_smoothing: float = 0.0, target_b: Optional[torch.Tensor] = None,
+                                    lam: float = 1.0, target_thresh: Optional[float] = None,
+                                    sum_classes: bool = False) -> torch.Tensor:
+    """``scale * binary_cross_entropy(logits, target, ...)``, and ``stats`` (fp64 [3]) += (that
+    loss, top-1 correct, top-min(5, C) correct) against the first label, as
+    ``cross_entropy_with_stats``: the forward sweep ranks the label on its way."""
+    e, l = _check_soft(target, label_smoothing, target_b, lam)
+    th = _check_thresh(target_thresh)
+    if _native_ce_ok(logits, target) and stats.is_cuda and stats.dtype == torch.float64 \
+            and stats.numel() == 3 and stats.is_contiguous():
+        _STATS["native"] += 1
+        tb = None if target_b is None else target_b.contiguous()
+        return _BinaryCrossEntropyFn.apply(logits, target.contiguous(), -100, float(scale), stats, e, tb, l, th,
+                                           bool(sum_classes))
+    _STATS["torch"] += 1
+    lf = logits.float()
+    loss = _torch_bce(lf, target, -100, e, target_b, l, th, bool(sum_classes)) * scale
+    _add_stats(stats, loss, lf, target)
     return loss

@@ -265,11 +265,18 @@ class Pipeline:
                  device: Optional[torch.device] = None, dtype: torch.dtype = torch.float32,
                  channels_last: bool = False, static_batch: Optional[int] = None,
                  fail_fast: bool = True, graphs: bool = False, kernel_grad_accum: bool = True,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, bce: bool = False, bce_target_thresh: Optional[float] = None,
+                 bce_sum: bool = False):
         if not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
         if label_smoothing and loss_fn is not None:
             raise ValueError("label_smoothing applies to the default loss only: smooth inside the custom loss_fn")
+        if not bce and (bce_target_thresh is not None or bce_sum):
+            raise ValueError("bce_target_thresh / bce_sum need bce=True")
+        if bce and loss_fn is not None:
+            raise ValueError("bce applies to the default loss only: a custom loss_fn replaces it")
+        if bce_target_thresh is not None and not 0.0 <= bce_target_thresh < 1.0:
+            raise ValueError(f"bce_target_thresh must be in [0, 1) or None, got {bce_target_thresh}")
         if schedule not in ("naive", "gpipe", "1f1b"):
             raise ValueError(f"unknown schedule {schedule!r}")
         if loss_on not in ("last", "first"):
@@ -285,6 +292,8 @@ class Pipeline:
             from ..ops.loss import cross_entropy as loss_fn  # fused HIP kernel on GPU
         self.loss_fn = loss_fn
         self.label_smoothing = float(label_smoothing)  # training micro-batches only; eval_step stays plain
+        # training micro-batches only: binary cross-entropy over the classes (None = softmax cross-entropy)
+        self.bce = dict(target_thresh=bce_target_thresh, sum_classes=bool(bce_sum)) if bce else None
         self.loss_on = loss_on if self.world > 1 else "last"
         self.device = torch.device(device) if device is not None else comm.device
         self.dtype = dtype
@@ -474,12 +483,18 @@ class Pipeline:
         when the stage uses the default loss on the GPU; else None."""
         from ..ops import loss as L
         if self.loss_fn is L.cross_entropy and stats.is_cuda and L._native_ce_ok(y, t):
+            if self.bce is not None:
+                return L.binary_cross_entropy_with_stats(y, t, 1.0 / self.micro_batches, stats,
+                                                         label_smoothing=self.label_smoothing, **self.bce)
             return L.cross_entropy_with_stats(y, t, 1.0 / self.micro_batches, stats,
                                               label_smoothing=self.label_smoothing)
         return None
 
     def _train_loss(self, logits: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-        """The training loss of one micro-batch (label smoothing: default loss only)."""
+        """The training loss of one micro-batch (label smoothing, bce: default loss only)."""
+        if self.bce is not None:
+            from ..ops.loss import binary_cross_entropy
+            return binary_cross_entropy(logits, t, label_smoothing=self.label_smoothing, **self.bce)
         if self.label_smoothing:
             return self.loss_fn(logits, t, label_smoothing=self.label_smoothing)
         return self.loss_fn(logits, t)

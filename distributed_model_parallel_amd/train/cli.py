@@ -22,6 +22,7 @@ Honoured flags the reference parsed but ignored (defect 4): ``-b``, ``-j``,
 from __future__ import annotations
 
 import argparse
+import functools
 import os
 import sys
 from typing import Optional
@@ -61,6 +62,10 @@ def check_args(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--lamb with --layer-decay is not supported")
     if not 0.0 <= args.label_smoothing < 1.0:
         parser.error("--label-smoothing must be in [0, 1)")
+    if not args.bce_loss and (args.bce_target_thresh is not None or args.bce_sum):
+        parser.error("--bce-target-thresh / --bce-sum need --bce-loss")
+    if args.bce_target_thresh is not None and not 0.0 <= args.bce_target_thresh < 1.0:
+        parser.error("--bce-target-thresh must be in [0, 1)")
     if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
         parser.error("--mixup-alpha / --cutmix-alpha must not be negative")
     mixing = args.mixup_alpha > 0 or args.cutmix_alpha > 0
@@ -202,6 +207,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--label-smoothing", default=0.0, type=float, metavar="E",
                    help="training loss: weight E spread uniformly over the classes, in [0, 1) "
                         "(validation loss stays plain)")
+    p.add_argument("--bce-loss", action="store_true",
+                   help="training loss: binary cross-entropy over the classes on the smoothed / mixed targets "
+                        "(timm's --bce-loss; composes with --label-smoothing, --mixup-alpha, --cutmix-alpha; "
+                        "validation loss stays the plain cross-entropy)")
+    p.add_argument("--bce-target-thresh", default=None, type=float, metavar="T",
+                   help="--bce-loss: targets above T become 1, the rest 0, in [0, 1) (timm's --bce-target-thresh, 0.2 in "
+                        "its recipes)")
+    p.add_argument("--bce-sum", action="store_true",
+                   help="--bce-loss: sum the loss over the classes, mean over the samples only")
     p.add_argument("--mixup-alpha", default=0.0, type=float, metavar="A",
                    help="mixup with lam ~ Beta(A, A) on the training batches (0 = off; not with --parallel pipe); "
                         "acc1_train stays top-1 against each sample's own (first) label")
@@ -371,7 +385,7 @@ def run_data_parallel(args, env) -> None:
     from ..utils.logging import MetricsLogger
     from ..utils.metrics import AverageMeter, accuracy
     from ..utils.precision import cast_model, parse_dtype
-    from ..ops.loss import cross_entropy
+    from ..ops.loss import binary_cross_entropy, cross_entropy
     from ..utils.profiling import trace_range
     from ..utils.schedule import build_schedule
     from ..utils.timers import StepTimer
@@ -469,6 +483,10 @@ def run_data_parallel(args, env) -> None:
         from ..ops.mix import BatchMixer
         mixer = BatchMixer(args.mixup_alpha, args.cutmix_alpha, prob=args.mix_prob, seed=args.seed,
                            rank=env.rank if args.parallel == "ddp" else 0)
+    train_loss = cross_entropy
+    if args.bce_loss:
+        train_loss = functools.partial(binary_cross_entropy, target_thresh=args.bce_target_thresh,
+                                       sum_classes=args.bce_sum)
     timer = StepTimer(dev)
     for epoch in range(start_epoch, args.epochs):
         if sampler is not None:
@@ -498,7 +516,7 @@ def run_data_parallel(args, env) -> None:
                 if mixer is not None:
                     x, y, y_b, lam = mixer(x, y)
                 out = net(x)
-                loss = cross_entropy(out, y, label_smoothing=args.label_smoothing, target_b=y_b, lam=lam)
+                loss = train_loss(out, y, label_smoothing=args.label_smoothing, target_b=y_b, lam=lam)
                 loss.backward()
                 opt.step()
                 opt.zero_grad()
@@ -589,7 +607,8 @@ def run_pipeline(args, env) -> None:
     pipe = Pipeline(model.as_sequential(), comm, (c, h, w), micro_batches=args.micro_batches,
                     schedule=args.schedule, dtype=parse_dtype(args.dtype),
                     channels_last=args.channels_last, partition=args.partition,
-                    label_smoothing=args.label_smoothing,
+                    label_smoothing=args.label_smoothing, bce=args.bce_loss,
+                    bce_target_thresh=args.bce_target_thresh, bce_sum=args.bce_sum,
                     # one GPU only (see train/step.py): multi-rank GPU pipelines run eagerly
                     graphs=env.device.type == "cuda" and not args.no_pipe_graphs and comm.size == 1)
     opt = _optimizer(args, pipe.module.parameters(), flat=False)

@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models import INPUT_SHAPES, build_model
-from ..ops.loss import cross_entropy
+from ..ops.loss import binary_cross_entropy, cross_entropy
 from ..ops.optim import build_optimizer
 from ..utils.precision import cast_model
 
@@ -47,6 +47,9 @@ class StepConfig:
     trust_coefficient: float = 1e-3  # optimizer == "lars"
     trust_ratio: bool = False       # optimizer == "adamw": per-tensor |w| / |update| on AdamW's step, i.e. LAMB
     label_smoothing: float = 0.0    # training loss (ops/loss.py); 0 = plain cross-entropy
+    bce: bool = False               # training loss: binary cross-entropy over the classes (timm's BinaryCrossEntropy)
+    bce_target_thresh: Optional[float] = None  # bce: targets above it become 1, the rest 0 (None = soft targets)
+    bce_sum: bool = False           # bce: sum over the classes (mean over the rows only)
     drop_path_rate: float = 0.0     # ViT / ConvNeXt / Swin: stochastic depth, linear over the blocks (ops/drop_path.py)
     ema_decay: float = 0.0          # weight EMA inside the optimizer's step kernels (ops/optim.py); 0 = off
     layer_decay: float = 1.0        # optimizer == "adamw", ViT / ConvNeXt: layer-wise lr decay (1 = off)
@@ -99,6 +102,18 @@ def _layer_scales(cfg: StepConfig, model: nn.Module):
     return layer_decay_scales(model, cfg.layer_decay)
 
 
+def _check_bce(cfg: StepConfig) -> None:
+    if not cfg.bce and (cfg.bce_target_thresh is not None or cfg.bce_sum):
+        raise ValueError("bce_target_thresh / bce_sum need bce=True")
+
+
+def _train_loss(cfg: StepConfig, out: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    if cfg.bce:
+        return binary_cross_entropy(out, y, label_smoothing=cfg.label_smoothing,
+                                    target_thresh=cfg.bce_target_thresh, sum_classes=cfg.bce_sum)
+    return cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
+
+
 def _optimizer(cfg: StepConfig, target, flat: bool, lr_scales=None) -> torch.optim.Optimizer:
     return build_optimizer(cfg.optimizer, target, flat, lr=cfg.lr, momentum=cfg.momentum,
                            weight_decay=cfg.weight_decay, betas=cfg.betas, eps=cfg.eps,
@@ -132,6 +147,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
     from ..parallel.distributed import DistributedDataParallel
     from ..parallel.sync_batchnorm import SyncBatchNorm
 
+    _check_bce(cfg)
     torch.manual_seed(cfg.seed)
     kw = {}
     if cfg.num_classes:
@@ -168,7 +184,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = wrapped(x)
-            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
+            loss = _train_loss(cfg, out, y)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -183,7 +199,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = wrapped(x)
-            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
+            loss = _train_loss(cfg, out, y)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -194,7 +210,7 @@ def _build_train_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
         def step() -> torch.Tensor:
             out = model(x)
-            loss = cross_entropy(out, y, label_smoothing=cfg.label_smoothing)
+            loss = _train_loss(cfg, out, y)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -218,6 +234,7 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
 
     if cfg.layer_decay != 1.0:
         raise ValueError("layer_decay with parallel='pipe' is not supported (per-stage optimizers see partial models)")
+    _check_bce(cfg)
     torch.manual_seed(cfg.seed)  # every rank builds the same full model, keeps its stage
     kw = {"num_classes": cfg.num_classes} if cfg.num_classes else {}
     model = build_model(cfg.model, **kw)
@@ -231,7 +248,8 @@ def build_pipeline_state(cfg: StepConfig, device: torch.device) -> TrainState:
                     schedule=cfg.schedule, device=device, dtype=cfg.dtype,
                     channels_last=cfg.channels_last, partition=cfg.partition,
                     static_batch=cfg.batch_size,  # every rank knows it: no per-step size message
-                    label_smoothing=cfg.label_smoothing,
+                    label_smoothing=cfg.label_smoothing, bce=cfg.bce,
+                    bce_target_thresh=cfg.bce_target_thresh, bce_sum=cfg.bce_sum,
                     # captured stage slots on one GPU only: the multi-stage slot
                     # schedule is verified on the CPU stand-ins (tests/test_pipeline.py)
                     # but never with RCCL between captured stages (a 1-GPU box cannot

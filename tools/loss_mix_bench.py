@@ -11,6 +11,13 @@
 * ``torch composition``: ``F.cross_entropy(x.float(), t, label_smoothing=0.1)`` and
   ``backward()`` -- the fp32 copy and the log-softmax / NLL chain.
 
+Then the binary cross-entropy (``csrc/loss/bce.hip``) at the same shapes, with smoothing
+0.1, a second label (lam 0.3) and the 0.2 target threshold: ``bce_fwd`` + ``bce_bwd``
+called directly, ``ops.loss.binary_cross_entropy`` and ``backward()``, and the torch
+composition (dense ``[B, C]`` target, fp32 copy of the logits,
+``F.binary_cross_entropy_with_logits``), beside the traffic floor: two reads and one
+write of ``[B, C]`` bf16 at the streaming ceiling.
+
 (b) ``batch_mix`` on bf16 channels-last ``[2048, 3, 224, 224]`` and ``[512, 3, 32, 32]``,
 mixup and CutMix (the box of lam = 0.5), against the leanest PyTorch forms:
 ``x.mul(lam).add_(x[perm], alpha=1 - lam)`` (gather, scaling, add) and a clone
@@ -94,6 +101,32 @@ def ce_configs(B: int, C: int, plain_only: bool) -> dict:
     return cfg
 
 
+def bce_configs(B: int, C: int) -> dict:
+    """Binary cross-entropy, smoothing 0.1 + target_b (lam 0.3) + threshold 0.2, forward + backward."""
+    from distributed_model_parallel_amd.ops.loss import _torch_bce, binary_cross_entropy
+    N = _native.require("loss_mix_bench")
+    g = torch.Generator().manual_seed(B)
+    x = (torch.randn(B, C, generator=g) * 3).bfloat16().cuda()
+    t = torch.randint(0, C, (B,), generator=g).cuda()
+    tb = torch.randint(0, C, (B,), generator=g).cuda()
+    one = torch.ones(1, device="cuda")
+    xa = x.clone().requires_grad_()
+
+    def native_calls():
+        _loss, stats = N.bce_fwd(x, t, -100, 1.0, None, 0.1, tb, 0.3, 0.2, False)
+        N.bce_bwd(one, x, t, stats, -100, 0.1, tb, 0.3, 0.2, False)
+
+    def op():
+        xa.grad = None
+        binary_cross_entropy(xa, t, label_smoothing=0.1, target_b=tb, lam=0.3, target_thresh=0.2).backward()
+
+    def composition():  # the dense target, the fp32 copy, F.binary_cross_entropy_with_logits
+        xa.grad = None
+        _torch_bce(xa.float(), t, -100, 0.1, tb, 0.3, 0.2, False).backward()
+
+    return {"bce, native calls": native_calls, "bce, binary_cross_entropy": op, "bce, torch composition": composition}
+
+
 def mix_configs(shape, dev: str = "cuda"):
     from distributed_model_parallel_amd.ops.mix import batch_mix
     B, _c, H, W = shape
@@ -151,6 +184,14 @@ def main(argv=None) -> int:
             print(f"| [{B}, {C}] | {k} | {statistics.median(ts):.4f} | {min(ts):.4f}-{max(ts):.4f} |", flush=True)
     if a.plain_only:
         return 0
+    print("\n| logits (bf16) | configuration, forward + backward | ms (median) | ms (min-max) | traffic floor, ms |")
+    print("|---|---|---|---|---|")
+    for s in a.ce_shapes.split(","):
+        B, C = (int(v) for v in s.split("x"))
+        floor = 3 * B * C * 2 / HBM_ACHIEVABLE_GBS / 1e6  # two reads and one write of [B, C] bf16
+        for k, ts in alternate(bce_configs(B, C), a.iters * 4, a.rounds).items():
+            print(f"| [{B}, {C}] | {k} | {statistics.median(ts):.4f} | {min(ts):.4f}-{max(ts):.4f} | {floor:.4f} |",
+                  flush=True)
     print("\n| batch (bf16, channels-last) | configuration | bytes needed | ms (median) | ms (min-max) | GB/s | "
           "of 6.3 TB/s | vs torch |")
     print("|---|---|---|---|---|---|---|---|")
