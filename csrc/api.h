@@ -300,6 +300,21 @@ std::vector<at::Tensor> layernorm_backward(const at::Tensor& dy, const at::Tenso
                                            const c10::optional<at::Tensor>& dres);
 bool layernorm_supported(int64_t D);
 
+// ---- norm/groupnorm.hip ----
+bool groupnorm_supported(int64_t C, int64_t G);
+std::vector<at::Tensor> groupnorm_forward(const at::Tensor& x, const c10::optional<at::Tensor>& weight,
+                                          const c10::optional<at::Tensor>& bias,
+                                          const c10::optional<at::Tensor>& residual, int64_t G,
+                                          double eps, bool act, double clip);
+std::vector<at::Tensor> groupnorm_backward(const at::Tensor& dy, const at::Tensor& x,
+                                           const c10::optional<at::Tensor>& y,
+                                           const c10::optional<at::Tensor>& weight,
+                                           const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
+                                           const at::Tensor& rstd, int64_t G, bool act, double clip,
+                                           bool want_dres, at::ScalarType param_dtype);
+std::map<std::string, int64_t> groupnorm_plan(int64_t N, int64_t HW, int64_t C, int64_t G,
+                                              at::ScalarType dtype);
+
 // ---- optim/fused_adamw.hip ----
 void flat_sumsq_partials(const at::Tensor& grad, at::Tensor& partials_row);
 void adamw_prepare(const c10::optional<at::Tensor>& partials, at::Tensor& hyper, at::Tensor& step,

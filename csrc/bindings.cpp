@@ -320,6 +320,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("layernorm_supported", &dmp::layernorm_supported);
 
+  // ---- GroupNorm (+ residual, + ReLU / ReLU6) on channels-last rows ----
+  m.def("groupnorm_supported", &dmp::groupnorm_supported, py::arg("C"), py::arg("G"));
+  m.def("groupnorm_forward", &dmp::groupnorm_forward, py::arg("x"), py::arg("weight"), py::arg("bias"),
+        py::arg("residual"), py::arg("G"), py::arg("eps"), py::arg("act"), py::arg("clip"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("groupnorm_backward", &dmp::groupnorm_backward, py::arg("dy"), py::arg("x"), py::arg("y"),
+        py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"), py::arg("G"), py::arg("act"),
+        py::arg("clip"), py::arg("want_dres"), py::arg("param_dtype"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("groupnorm_plan", &dmp::groupnorm_plan, py::arg("N"), py::arg("HW"), py::arg("C"), py::arg("G"),
+        py::arg("dtype"));
+
   // ---- NHWC max pooling with byte argmax ----
   m.def("maxpool2d_forward", &dmp::maxpool2d_forward,
         py::call_guard<py::gil_scoped_release>());

@@ -110,6 +110,8 @@ FEATURES = {
     "random_erase": "random erasing's in-place kernel with per-pixel Philox noise (random_erase.hip, "
                     "data/random_erase.py) -> the PyTorch composition, box by box",
     "dwconv7":"native 7x7 depthwise conv of the ConvNeXt blocks (depthwise7.hip, ops/depthwise7.py) -> F.conv2d (MIOpen)",
+    "groupnorm": "native GroupNorm (+ residual, + ReLU / ReLU6) on LDS-resident kernels (groupnorm.hip, "
+                 "ops/groupnorm.py) -> the PyTorch composition",
     "async_wgrad": "weight gradients on a side stream beside the data-gradient chain (ops/wgrad_stream.py) "
                    "-> inline on the compute stream",
 }

@@ -1,4 +1,4 @@
-"""Model zoo: MobileNetV2 (CIFAR, with/without BN), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B, ConvNeXt V2,
+"""Model zoo: MobileNetV2 (CIFAR, with BN, with GroupNorm, without a norm), ResNet-18..152, ViT-B/16, ConvNeXt-T/S/B, ConvNeXt V2,
 Swin-T/S/B."""
 from __future__ import annotations
 
@@ -7,8 +7,8 @@ from typing import Callable, Dict
 import torch.nn as nn
 
 from .mobilenetv2 import (HeadPool, InvertedResidual, MobileNetV2, mobilenet_v2, mobilenet_v2_224,
-                          mobilenet_v2_nobn)
-from .resnet import BasicBlock, Bottleneck, ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
+                          mobilenet_v2_gn, mobilenet_v2_nobn)
+from .resnet import BasicBlock, Bottleneck, ResNet, resnet18, resnet34, resnet50, resnet50_gn, resnet101, resnet152
 from .convnext import (ConvNeXt, ConvNeXtBlock, convnext_base, convnext_small, convnext_test, convnext_tiny,
                        convnextv2_base, convnextv2_large, convnextv2_nano, convnextv2_pico, convnextv2_test,
                        convnextv2_tiny)
@@ -19,10 +19,12 @@ from .layer_decay import layer_decay_scales, layer_ids
 MODELS: Dict[str, Callable[..., nn.Module]] = {
     "mobilenetv2": mobilenet_v2,
     "mobilenetv2_nobn": mobilenet_v2_nobn,
+    "mobilenetv2_gn": mobilenet_v2_gn,
     "mobilenetv2_224": mobilenet_v2_224,
     "resnet18": resnet18,
     "resnet34": resnet34,
     "resnet50": resnet50,
+    "resnet50_gn": resnet50_gn,
     "resnet101": resnet101,
     "resnet152": resnet152,
     "vit_b_16": vit_b_16,
@@ -47,10 +49,12 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
 INPUT_SHAPES = {
     "mobilenetv2": ((3, 32, 32), 10),
     "mobilenetv2_nobn": ((3, 32, 32), 10),
+    "mobilenetv2_gn": ((3, 32, 32), 10),
     "mobilenetv2_224": ((3, 224, 224), 1000),
     "resnet18": ((3, 224, 224), 1000),
     "resnet34": ((3, 224, 224), 1000),
     "resnet50": ((3, 224, 224), 1000),
+    "resnet50_gn": ((3, 224, 224), 1000),
     "resnet101": ((3, 224, 224), 1000),
     "resnet152": ((3, 224, 224), 1000),
     "vit_b_16": ((3, 224, 224), 1000),
@@ -90,8 +94,8 @@ def classifier_name(model: nn.Module) -> str:
 
 __all__ = ["MODELS", "INPUT_SHAPES", "build_model", "classifier_name", "layer_ids", "layer_decay_scales",
            "MobileNetV2", "InvertedResidual", "HeadPool",
-           "mobilenet_v2", "mobilenet_v2_nobn", "mobilenet_v2_224", "ResNet", "BasicBlock", "Bottleneck", "resnet18",
-           "resnet34", "resnet50", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
+           "mobilenet_v2", "mobilenet_v2_nobn", "mobilenet_v2_gn", "mobilenet_v2_224", "ResNet", "BasicBlock", "Bottleneck", "resnet18",
+           "resnet34", "resnet50", "resnet50_gn", "resnet101", "resnet152", "VisionTransformer", "vit_b_16",
            "vit_tiny", "ConvNeXt", "ConvNeXtBlock", "convnext_tiny", "convnext_small", "convnext_base",
            "convnext_test", "convnextv2_pico", "convnextv2_nano", "convnextv2_tiny", "convnextv2_base",
            "convnextv2_large", "convnextv2_test", "SwinTransformer", "swin_tiny", "swin_small", "swin_base",

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from ..ops.batchnorm import BatchNormAct2d
 from ..ops.conv1x1 import Conv1x1
 from ..ops.depthwise import DepthwiseConv2d
+from ..ops.groupnorm import GroupNormAct2d
 from ..ops.fused import GradSlot, conv_bn, grad_tap
 from ..ops.pool import global_avg_pool
 from ..ops.stem import RowTapConv2d
@@ -56,12 +57,28 @@ IMAGENET_SETTINGS: Tuple[Tuple[int, int, int, int], ...] = (
 )
 
 
-def _norm(ch: int, use_bn: bool, act: bool, activation: str = "relu") -> nn.Module:
-    """BN(+activation) fused in one kernel, or the bare activation without BN.
+GN_CHANNELS_PER_GROUP = 8  # norm="gn": every width of both settings tables divides by 8
+
+
+def _norm_kind(use_bn, norm: str | None = "_from_use_bn") -> str | None:
+    """"bn" / "gn" / None from the ``norm`` argument, or from the older ``use_bn`` flag."""
+    if norm == "_from_use_bn":
+        norm = use_bn if isinstance(use_bn, str) or use_bn is None else ("bn" if use_bn else None)
+    if norm not in ("bn", "gn", None):
+        raise ValueError(f"norm must be 'bn', 'gn' or None, got {norm!r}")
+    return norm
+
+
+def _norm(ch: int, use_bn, act: bool, activation: str = "relu") -> nn.Module:
+    """BN or GN (+activation) fused in one kernel, or the bare activation without
+    a norm.  ``use_bn``: True / "bn", "gn" (8 channels per group), or False / None.
     ``activation``: "relu" (the reference's CIFAR model) or "relu6" (the
     torchvision-style 224-px model)."""
-    if use_bn:
+    kind = _norm_kind(use_bn)
+    if kind == "bn":
         return BatchNormAct2d(ch, act=activation if act else None)
+    if kind == "gn":
+        return GroupNormAct2d(ch // GN_CHANNELS_PER_GROUP, ch, act=activation if act else None)
     if not act:
         return nn.Identity()
     return nn.ReLU6(inplace=False) if activation == "relu6" else nn.ReLU(inplace=False)
@@ -81,8 +98,9 @@ class InvertedResidual(nn.Module):
 
     def __init__(self, cin: int, cout: int, expansion: int, stride: int,
                  use_bn: bool = True, shortcut_bn: bool | None = None, imagenet: bool = False,
-                 activation: str = "relu"):
+                 activation: str = "relu", norm: str | None = "_from_use_bn"):
         super().__init__()
+        use_bn = _norm_kind(use_bn, norm)  # "bn" / "gn" / None from here on
         hidden = cin * expansion
         self.stride = stride
         # 1x1 convs run as the MFMA GEMM and the depthwise as the NHWC kernel on
@@ -100,7 +118,7 @@ class InvertedResidual(nn.Module):
         if stride == 1 and cin != cout and not imagenet:
             mods: List[nn.Module] = [Conv1x1(cin, cout)]
             if sc_bn:
-                mods.append(BatchNormAct2d(cout, act=None))
+                mods.append(_norm(cout, sc_bn, act=False))
             self.shortcut = nn.Sequential(*mods)
         else:
             self.shortcut = nn.Sequential()
@@ -150,9 +168,11 @@ class MobileNetV2(nn.Module):
     def __init__(self, num_classes: int = 10, use_bn: bool = True,
                  settings: Sequence[Tuple[int, int, int, int]] = CIFAR_SETTINGS,
                  nobn_shortcut_bn: bool = False, imagenet: bool = False, dropout: float = 0.0,
-                 activation: str = "relu"):
+                 activation: str = "relu", norm: str | None = "_from_use_bn"):
         super().__init__()
-        self.use_bn = use_bn
+        self.norm = _norm_kind(use_bn, norm)
+        self.use_bn = self.norm == "bn"
+        use_bn = self.norm
         if imagenet:
             # 224-px stem: 3x3 / stride 2 (the library conv; 3 input channels)
             self.conv1 = nn.Conv2d(3, 32, 3, stride=2, padding=1, bias=False)
@@ -209,6 +229,13 @@ def mobilenet_v2(num_classes: int = 10, **kw) -> MobileNetV2:
 
 def mobilenet_v2_nobn(num_classes: int = 10, **kw) -> MobileNetV2:
     return MobileNetV2(num_classes=num_classes, use_bn=False, **kw)
+
+
+def mobilenet_v2_gn(num_classes: int = 10, **kw) -> MobileNetV2:
+    """GroupNorm (8 channels per group) in every BN's place: per-sample
+    statistics, so pipeline micro-batches and small per-GPU batches normalise
+    exactly as the full batch does."""
+    return MobileNetV2(num_classes=num_classes, norm="gn", **kw)
 
 
 def mobilenet_v2_224(num_classes: int = 1000, **kw) -> MobileNetV2:

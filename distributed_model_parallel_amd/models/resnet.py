@@ -21,6 +21,7 @@ from ..ops.batchnorm import BatchNormAct2d
 from ..ops.bn_fold import conv1x1_bn_fold, foldable, foldable_downsample
 from ..ops.conv1x1 import Conv1x1
 from ..ops.conv_igemm import ConvIG2d
+from ..ops.groupnorm import GroupNormAct2d
 from ..ops.fused import GradSlot, bn_relu_conv1x1, conv_bn, conv_bn_maxpool, grad_tap
 from ..ops.pool import MaxPool2d, global_avg_pool
 from ..ops.stem import StemConv2d
@@ -49,6 +50,20 @@ def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     return Conv1x1(cin, cout, stride)
 
 
+GN_GROUPS = 32  # norm="gn": Wu & He's setting
+
+
+def _norm2d(norm: str, ch: int, act: Optional[str]) -> nn.Module:
+    """BN or GN (+ residual, + ReLU) in one kernel.  With GN the conv -> norm pairs
+    run through conv_bn's plain branch: the fused-moment, bn-fold and stem-pool
+    fusions are BN-only and are not taken."""
+    if norm == "bn":
+        return BatchNormAct2d(ch, act=act)
+    if norm == "gn":
+        return GroupNormAct2d(GN_GROUPS, ch, act=act)
+    raise ValueError(f"norm must be 'bn' or 'gn', got {norm!r}")
+
+
 def _shortcut(ds: Optional[nn.Module], x: torch.Tensor) -> torch.Tensor:
     if ds is None:
         return x
@@ -61,12 +76,12 @@ class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, cin: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, norm: str = "bn"):
         super().__init__()
         self.conv1 = _conv3x3(cin, planes, stride)
-        self.bn1 = BatchNormAct2d(planes, act="relu")
+        self.bn1 = _norm2d(norm, planes, "relu")
         self.conv2 = _conv3x3(planes, planes)
-        self.bn2 = BatchNormAct2d(planes, act="relu")  # fused: relu(bn2(x) + identity)
+        self.bn2 = _norm2d(norm, planes, "relu")  # fused: relu(bn2(x) + identity)
         self.downsample = downsample
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -79,14 +94,14 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, norm: str = "bn"):
         super().__init__()
         self.conv1 = _conv1x1(cin, planes)
-        self.bn1 = BatchNormAct2d(planes, act="relu")
+        self.bn1 = _norm2d(norm, planes, "relu")
         self.conv2 = _conv3x3(planes, planes, stride)  # stride on the 3x3 (ResNet v1.5)
-        self.bn2 = BatchNormAct2d(planes, act="relu")
+        self.bn2 = _norm2d(norm, planes, "relu")
         self.conv3 = _conv1x1(planes, planes * 4)
-        self.bn3 = BatchNormAct2d(planes * 4, act="relu")  # fused residual add + relu
+        self.bn3 = _norm2d(norm, planes * 4, "relu")  # fused residual add + relu
         self.downsample = downsample
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -129,12 +144,13 @@ class Bottleneck(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int],
                  num_classes: int = 1000, zero_init_residual: bool = False,
-                 stem_channels: int = 64):
+                 stem_channels: int = 64, norm: str = "bn"):
         super().__init__()
+        self.norm = norm
         self.inplanes = stem_channels
         # 7x7/s2 stem as a space-to-depth MFMA implicit GEMM with fused BN moments
         self.conv1 = StemConv2d(3, stem_channels)
-        self.bn1 = BatchNormAct2d(stem_channels, act="relu")
+        self.bn1 = _norm2d(norm, stem_channels, "relu")
         self.maxpool = MaxPool2d(3, stride=2, padding=1)  # NHWC kernel, byte argmax
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
@@ -145,7 +161,7 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
         if zero_init_residual:
@@ -160,12 +176,12 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(
                 _conv1x1(self.inplanes, planes * block.expansion, stride),
-                BatchNormAct2d(planes * block.expansion, act=None),
+                _norm2d(self.norm, planes * block.expansion, None),
             )
-        mods: List[nn.Module] = [block(self.inplanes, planes, stride, downsample)]
+        mods: List[nn.Module] = [block(self.inplanes, planes, stride, downsample, norm=self.norm)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            mods.append(block(self.inplanes, planes))
+            mods.append(block(self.inplanes, planes, norm=self.norm))
         return nn.Sequential(*mods)
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
@@ -196,6 +212,11 @@ def resnet34(num_classes: int = 1000, **kw) -> ResNet:
 
 def resnet50(num_classes: int = 1000, **kw) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, **kw)
+
+
+def resnet50_gn(num_classes: int = 1000, **kw) -> ResNet:
+    """ResNet-50 with GroupNorm(32) in every BN's place (Wu & He, 2018)."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, norm="gn", **kw)
 
 
 def resnet101(num_classes: int = 1000, **kw) -> ResNet:

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from .batchnorm import BatchNormAct2d
+from .groupnorm import GroupNormAct2d
 
 
 class GradSlot:
@@ -93,7 +94,7 @@ def conv_bn(conv: nn.Module, bn: nn.Module, x: torch.Tensor,
             y, sums = conv.forward_with_moments(x)
         return bn(y, residual, sums=sums)
     y = conv(x)
-    if isinstance(bn, BatchNormAct2d):
+    if isinstance(bn, (BatchNormAct2d, GroupNormAct2d)):  # residual add (+ ReLU) inside the norm's pass
         return bn(y, residual)
     if residual is not None:
         return bn(y) + residual
